@@ -1,6 +1,8 @@
 """VO training-step throughput on MI355X (BASELINE.json metric: frames/s of 3-frame 640x480 snippets).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+    python bench.py --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -8,15 +10,22 @@ A step = zero_grad -> DepthNet + 2x PoseNet forward -> fused 4-scale view-synthe
 -> [bucketed RCCL gradient all-reduce] -> Adam, on one batch of synthetic triplets already resident in
 HBM.  Default workload: BASELINE.json configs[2]/[3] per GPU (batch 12, 4 scales,
 ResNet-18, fp32); `--config c2` selects configs[1] (batch 4, single scale).  Weak scaling: the
-per-GPU batch is fixed, `value` is the whole-job frames/s = 3 * B * N / t_step (max over ranks).
-Rank 0 prints one JSON line with `roofline` (dominant hand-written kernel class; its launches are HIP-event timed
-over 5 further SINGLE-STREAM steps run right after the timed region -- the timed steps overlap four streams, where an
-event pair would measure how long a kernel shared the chip) and, at N=1, `cpu_baseline` (the oracle's PyTorch-CPU
-restatement of the same step at the same batch), `stock_caller` (the literal vo/train.py:173-199 sequence: per-parameter
-torch.optim.Adam, zero_grad(set_to_none=True), five .detach().cpu() per step) and `loss_check` (the first-step loss
-against the committed oracle value, tests/golden/bench_loss.json).  `ms_per_step` is the mean over the K timed steps
-(what `value` is computed from); `median_ms_per_step` is the median of the K per-step intervals taken from events
-recorded on the main stream (BASELINE.md section 2 defines the metric on the median of >= 50 steps: the default K).
+per-GPU batch is fixed, `value` is the whole-job frames/s = 3 * B * N / t_step (max over ranks).  The Adam pass runs at
+lr 0 (TIMED_LR): the same work, but every step computes from the seeded weights, so runs are comparable output for output.
+
+A plain run only sets up, warms up, times the K steps, writes the last timed step's outputs when `--dump-outputs DIR`
+is given (dump_outputs below) and prints one JSON line.  `ms_per_step` is the mean over the K timed steps (what `value`
+is computed from); `median_ms_per_step` is the median of the K per-step intervals taken from events recorded on the main
+stream (BASELINE.md section 2 defines the metric on the median of >= 50 steps: the default K).
+
+`--full` adds everything else, after the timed region unless stated: `loss_check` (the first-step loss against the
+committed oracle value, tests/golden/bench_loss.json; checked before the warm-up), `roofline` (dominant hand-written kernel
+class; its launches are HIP-event timed over 5 further SINGLE-STREAM steps -- the timed steps overlap four streams, where
+an event pair would measure how long a kernel shared the chip), `measured_peaks`, and at N=1 `cpu_baseline` (the
+oracle's PyTorch-CPU restatement of the same step at the same batch), `stock_caller` (the literal vo/train.py:173-199
+sequence: per-parameter torch.optim.Adam, zero_grad(set_to_none=True), five .detach().cpu() per step) and
+`other_configs` (configs[1], the bf16 mode, configs[0] inference, configs[4] Depth-Anything-V2).  The `--no-*` switches
+drop single legs of a `--full` run.
 """
 import argparse
 import json
@@ -51,7 +60,14 @@ def train_config(batch, num_scales):
                           auto_mask=True, ssim_ratio=0.85, min_depth=0.1, max_depth=10.0, use_compile=False)}
 
 
-def build_gpu(batch, num_scales, device, rank, comm=None):
+# The timed steps run the fused Adam pass with lr 0: the kernel still reads and writes every weight and moment and the
+# data-gradient packs are still refreshed, so a step's work is unchanged, but the weights stay the seeded ones.  Every step
+# therefore computes from the same inputs, and two runs differ only by one step's rounding (float atomics), not by a
+# trajectory of Adam updates that amplifies it (Adam moves a weight whose tiny gradient changes sign by a whole lr).
+TIMED_LR = 0.0
+
+
+def build_gpu(batch, num_scales, device, rank, comm=None, lr=1e-4):
     from deep_visual_slam_amd import dp, synth
     from deep_visual_slam_amd.depthnet import DepthNet
     from deep_visual_slam_amd.learner_new import MonodepthTrainer
@@ -64,18 +80,60 @@ def build_gpu(batch, num_scales, device, rank, comm=None):
     trainer.num_scales = num_scales
     hook_streams = ({id(p): trainer.pose_stream for p in pose_net.parameters()} if trainer.pose_stream is not None else None)
     sync = dp.GradSync(flat, hook_streams=hook_streams, comm=comm)
-    opt = dp.FusedAdam(flat, lr=1e-4)
+    opt = dp.FusedAdam(flat, lr=lr)
     sample = synth.throughput_sample(batch, H, W, rank=rank, device=device)
     return trainer, flat, sync, opt, sample
 
 
-def gpu_step(trainer, sync, opt, sample):
-    """vo/train.py:173-199 train_mono_step: forward, backward, all-reduce, Adam (+ fused zero_grad)."""
-    _, losses = trainer.process_batch(sample)
+def train_step(trainer, sync, opt, sample):
+    """vo/train.py:173-199 train_mono_step: forward, backward, all-reduce, Adam (+ fused zero_grad); returns (outputs, losses)."""
+    outputs, losses = trainer.process_batch(sample)
     losses["loss"].backward()
     sync.finish()
     opt.step(grad_scale=sync.grad_scale, zero_grad=True)
-    return losses
+    return outputs, losses
+
+
+def gpu_step(trainer, sync, opt, sample):
+    """train_step's losses only (the warm-up, the --full legs, and the tools that import this file)."""
+    return train_step(trainer, sync, opt, sample)[1]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WHOLE_MAX = 1 << 22           # an output with more elements is written as a fixed seeded sample of DUMP_SAMPLE of them
+DUMP_SAMPLE = 1 << 21
+
+
+def _seeded_sample(t, n, seed):
+    """`n` elements of `t` (flattened) at sorted positions drawn without replacement from numpy's default_rng(seed): the same
+    positions for the same numel, run after run."""
+    import numpy as np
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), size=n, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(path, outputs, losses):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array --
+    the losses (float64 scalars: loss, loss_0 ... loss_{S-1}) and the DepthNet / PoseNet entries of `outputs` (disp_<s>,
+    axisangle_0_<f>, translation_0_<f>, cam_T_cam_0_<f>; float32; the lazy view-synthesis entries are not materialised).
+    An output of more than DUMP_WHOLE_MAX elements (a --batch override) is written as <name>_sample: DUMP_SAMPLE of its
+    elements at seeded positions.  The inputs are seeded and the weights fixed (TIMED_LR), so two runs differ only by the
+    rounding of the step's float atomics."""
+    import numpy as np
+    arrays = {k.replace("/", "_"): v.detach().double() for k, v in losses.items()}
+    for i, (k, v) in enumerate(sorted(dict.items(outputs), key=lambda kv: str(kv[0]))):    # no materialisation
+        name = "_".join(str(p) for p in k) if isinstance(k, tuple) else str(k)
+        v = v.detach().float()
+        if v.numel() > DUMP_WHOLE_MAX:
+            name, v = name + "_sample", _seeded_sample(v, DUMP_SAMPLE, 1 + i)
+        arrays[name] = v
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def build_stock(batch, num_scales, device, rank):
@@ -109,14 +167,15 @@ def stock_step(trainer, opt, sample):
 
 
 def fresh_process_config(config, steps, warmup, extra=()):
-    """`python bench.py --config <config>` as a CHILD process (never an exec: this process has initialised the GPU); returns the
+    """`python bench.py --full --config <config>` with only the loss check of the `--full` legs, as a CHILD process (never an
+    exec: this process has initialised the GPU); returns the
     child's JSON line, or None when it cannot run (under a profiler's preload, or on any failure -- the in-process figure stays)."""
     import subprocess
     import sys
     if any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", ""):
         return None
     cmd = [sys.executable, os.path.abspath(__file__), "--config", config, "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu-baseline", "--no-other-configs", "--no-kernel-timing", "--no-stock-caller"] + list(extra)
+           "--full", "--no-cpu-baseline", "--no-other-configs", "--no-kernel-timing", "--no-stock-caller"] + list(extra)
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         for line in reversed(r.stdout.strip().splitlines()):
@@ -481,7 +540,15 @@ def main():
                          "fp32 accumulate) -- a separately labelled measurement, never the headline")
     ap.add_argument("--serialize", action="store_true",
                     help="run the timed region on one stream too (what the rocprofv3 per-kernel passes use)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the loss check, the per-kernel roofline, the measured peaks, the CPU baseline, the stock caller and the "
+                         "other configurations (the --no-* switches drop single legs); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, network outputs, a seeded sample of the updated "
+                         "weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     cfg = CONFIGS[args.config]
     batch = args.batch or cfg["batch"]
@@ -541,7 +608,7 @@ def main():
         if int(flag) == 0:
             comm = None
             comm_note = "direct RCCL communicator failed its self-test on some rank (%s): torch.distributed carries the buckets" % (comm_note or "this rank was fine")
-    trainer, flat, sync, opt, sample = build_gpu(batch, num_scales, device, rank, comm=comm)
+    trainer, flat, sync, opt, sample = build_gpu(batch, num_scales, device, rank, comm=comm, lr=TIMED_LR)
 
     def barrier():
         if world > 1:
@@ -559,7 +626,7 @@ def main():
     if args.serialize:
         set_concurrency(False)
     check = None
-    if rank == 0 and not args.no_loss_check and args.batch is None:
+    if args.full and rank == 0 and not args.no_loss_check and args.batch is None:
         check = loss_check(trainer, sample, args.config)
         if check is not None and not check["ok"]:
             raise SystemExit("bench.py: first-step loss %.8f differs from the oracle's %.8f (rel %.2e): refusing to time a "
@@ -573,17 +640,22 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        losses = gpu_step(trainer, sync, opt, sample)
+        outputs, losses = train_step(trainer, sync, opt, sample)
         marks[i + 1].record()
+        if i + 1 < args.steps:
+            outputs = None                    # as in gpu_step: only the last step's outputs outlive the step (--dump-outputs)
     barrier()
     dt = time.perf_counter() - t0
     intervals = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = intervals[len(intervals) // 2] if len(intervals) % 2 else 0.5 * (intervals[len(intervals) // 2 - 1] + intervals[len(intervals) // 2])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, losses)
+    del outputs
     # per-kernel durations for the roofline: HIP events around every launch of the library, over further steps
     # of the same loop run on ONE stream -- with DepthNet, PoseNet and the weight gradients overlapping on four
     # streams an event pair measures how long a kernel shared the chip, not how long it needs
     prof, prof_steps = {}, 0
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         set_concurrency(False)
         gpu_step(trainer, sync, opt, sample)
         barrier()
@@ -639,7 +711,7 @@ def main():
                                      "fewer MFMA flops than counted (DVS_WINOGRAD=0 / DVS_WINOGRAD_WGRAD=0 / "
                                      "DVS_WINOGRAD_DECODER_WGRAD=0 time the direct kernels)")
             roof.update(pmc_traffic(args.config, roof["kernel"]))
-        peaks = measured_peaks(device)
+        peaks = measured_peaks(device) if args.full else None
         if roof is not None:
             roof["peak_measured"] = peaks["mfma_f32_TFLOPs"] if roof["bound"] == "mfma" else peaks["hbm_copy_GBps"]
             roof["frac_of_measured"] = roof["achieved"] / roof["peak_measured"]
@@ -665,16 +737,19 @@ def main():
                           "outputs": "lazy (the per-scale view-synthesis tensors of `outputs` are materialised on first access, "
                                      "SURVEY.md section 8d; config Train.materialize_outputs times the eager variant)",
                           "streams": "single" if args.serialize else "depth | pose | 2x weight-gradient",
+                          "optimizer": "fused Adam pass at lr %g: every step computes from the seeded weights" % TIMED_LR,
                           "allreduce": (None if world == 1 else ("rccl-direct (include/dvslam_rccl.h)" if comm is not None else "torch.distributed " + dist.get_backend()
                                                                       + (" -- " + comm_note if comm_note else ""))),
                           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "default (4)")},
-               "loss": loss_val, "loss_check": check,
-               "kernels_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
-               "conv_kernels": conv_summary,
-               "roofline": roof, "roofline_chain": chain, "measured_peaks": peaks}
-        if world == 1 and not args.no_cpu_baseline:
+               "loss": loss_val}
+        if args.full:
+            out.update({"loss_check": check,
+                        "kernels_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
+                        "conv_kernels": conv_summary,
+                        "roofline": roof, "roofline_chain": chain, "measured_peaks": peaks})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch or batch, num_scales)
-        if world == 1 and args.config == "c3" and not args.no_other_configs:
+        if args.full and world == 1 and args.config == "c3" and not args.no_other_configs:
             # BASELINE.json configs[1] (batch 4, single-scale loss) beside the headline workload: same code path,
             # same timing discipline, reported for reference -- `value` above is the batch-12 4-scale step
             del trainer, flat, sync, opt, sample, losses, pose_stream
@@ -691,7 +766,7 @@ def main():
                 gc.collect()
                 torch.cuda.empty_cache()
             c2 = CONFIGS["c2"]
-            tr2, _, sync2, opt2, sample2 = build_gpu(c2["batch"], c2["num_scales"], device, rank)
+            tr2, _, sync2, opt2, sample2 = build_gpu(c2["batch"], c2["num_scales"], device, rank, lr=TIMED_LR)
             check2 = loss_check(tr2, sample2, "c2") if not args.no_loss_check else None
             for _ in range(args.warmup):
                 gpu_step(tr2, sync2, opt2, sample2)
