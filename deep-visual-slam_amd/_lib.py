@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstri
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVS_LIB") or os.path.join(HERE, "libdvslam_hip.so")    # DVS_LIB: A/B builds (tools/build_variant.py)
 MAX_SCALES = 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _vp = C.c_void_p
 
@@ -56,6 +56,12 @@ class ConvFusion(C.Structure):
     _fields_ = [("x2", _vp), ("C1", C.c_int), ("in_scale", _vp), ("in_shift", _vp), ("in_relu", C.c_int),
                 ("nchw_planar", C.c_int), ("act", C.c_int), ("stats", _vp), ("stat_groups", C.c_int), ("residual", _vp),
                 ("stat_slots", C.c_int)]
+
+
+class CloudCfg(C.Structure):
+    _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("stride_y", C.c_int), ("stride_x", C.c_int),
+                ("from_disp", C.c_int), ("compact", C.c_int), ("k_row_stride", C.c_int),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float)]
 
 
 _SIGNATURES = {
@@ -160,6 +166,10 @@ _SIGNATURES = {
     "dvs_depth_loss_workspace": (C.c_size_t, [C.POINTER(DepthLossCfg)]),
     "dvs_depth_loss_fwd": (C.c_int, [C.POINTER(DepthLossCfg), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dvs_depth_loss_bwd": (C.c_int, [C.POINTER(DepthLossCfg), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "dvs_cloud_capacity": (C.c_int, [C.POINTER(CloudCfg), C.POINTER(C.c_int)]),
+    "dvs_cloud_workspace": (C.c_size_t, [C.POINTER(CloudCfg)]),
+    "dvs_cloud_fwd": (C.c_int, [C.POINTER(CloudCfg)] + [_vp] * 9),
+    "dvs_pose_chain": (C.c_int, [_vp] * 6 + [C.c_int, _vp]),
 }
 
 _lib = None

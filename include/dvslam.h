@@ -589,6 +589,46 @@ int dvs_vit_assemble(const float* patch_tokens, const float* cls_token, const fl
 int dvs_resize_bilinear_ac(const float* x, float* y, int B, int h, int w, int H, int W, int C, void* stream);
 int dvs_deconv_shuffle(const float* g, float* y, int B, int h, int w, int k, int Cout, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 9) output stage of the inference path: world pose chain and coloured point cloud
+ *     replaces the per-frame host work of the three inference callers after the two networks:
+ *       ros2_ws/src/vo_visualizer/vo_visualizer/visualizer_node.py:26-56,128-191 (meshgrid, back-projection, colours,
+ *         create_pointcloud2's 16-byte records, world_pose @ T, quaternion of the world pose),
+ *       vo/predict.py:69-98 + vo/utils/visualization.py:157-193 (the same + world_pose @ points + the y flip),
+ *       vo/eval_traj.py:85-121,138-147 (z > 0 mask in pixel order, K^-1, T_global @ points, T_global @= T_local).
+ *
+ *   Per kept pixel (v, u) of image b, in fp32:
+ *       z = depth[b,0,v,u]     or, from_disp:  z = 1 / (1/max_depth + (1/min_depth - 1/max_depth) * disp[b,0,v,u])
+ *       x = (u - cx) / fx * z,  y = (v - cy) / fy * z         fx, fy, cx, cy read on the device from K[b]
+ *       p = M[b] . (x, y, z, 1)                               M = NULL: camera frame
+ *       record = { p.x, p.y, p.z, bit-cast<float>(r << 16 | g << 8 | b) },  c = (uint8) clamp(image[b,c,v,u] * 255, 0, 255)
+ *   Kept pixels: (i * stride_y, j * stride_x); capacity per image n_max = ceil(H / stride_y) * ceil(W / stride_x).
+ *   compact = 0: every kept pixel is written, record k is kept pixel k in row-major order, count[b] = n_max.
+ *   compact = 1: only pixels with z_lo < z and (z_hi > 0: z < z_hi) are written, contiguous from records[b][0] in row-major
+ *       pixel order (numpy boolean-mask order); count[b] is their number; nothing at or beyond records[b][count[b]] is
+ *       touched.  Needs `workspace` (dvs_cloud_workspace bytes, device).  index (optional): v * W + u of every record.
+ *   depth_or_disp [B,1,H,W], image [B,3,H,W], K [B,k_row_stride,k_row_stride] (3 or 4), M [B,4,4] or NULL,
+ *   records [B,n_max,4] (16-byte aligned), count [B] int32, index [B,n_max] int32 or NULL.  All device memory.
+ *
+ *   dvs_pose_chain: world <- world . T[b] for b = 0 .. B-1; after step b: poses[b] = world, M[b] = left . world (left NULL:
+ *       M[b] = world), tq[b] = (tx, ty, tz, qx, qy, qz, qw) of world with a unit quaternion, qw >= 0.  T [B,4,4], left [4,4] or
+ *       NULL, world [4,4] updated in place (persistent device state), poses / M [B,4,4] or NULL, tq [B,7] or NULL.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, H, W;
+    int stride_y, stride_x;          /* >= 1 */
+    int from_disp;                   /* 1: the input is ("disp", 0) and disp_to_depth (model/layers.py:16-26) is applied inside */
+    int compact;
+    int k_row_stride;                /* 3 or 4 */
+    float min_depth, max_depth;      /* from_disp only */
+    float z_lo, z_hi;                /* compact only; z_hi <= 0: no upper bound */
+} dvs_cloud_cfg;
+int dvs_cloud_capacity(const dvs_cloud_cfg* cfg, int* n_max);
+size_t dvs_cloud_workspace(const dvs_cloud_cfg* cfg);
+int dvs_cloud_fwd(const dvs_cloud_cfg* cfg, const float* depth_or_disp, const float* image, const float* K, const float* M,
+                  float* records, int* count, int* index, void* workspace, void* stream);
+int dvs_pose_chain(const float* T, const float* left, float* world, float* poses, float* M, float* tq, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
