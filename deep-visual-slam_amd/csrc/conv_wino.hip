@@ -706,7 +706,10 @@ __global__ __launch_bounds__(NT, 1) void wino_wgrad_kernel(WinoWgradParams p) {
             dl = cl >= Ws ? (int)OOB_COL : 0;
         } else if constexpr (MODE == 1) {
             df = pc == 0 ? 2 * (int)Cin4 : 0;              // column -1 -> 1
-            const int cm = max(2 * (Ws - 1) - cl, cstep * (NP - 1) - 1);     // (column W + 1 only meets a masked dY column: any finite value does)
+            // (column W + 1 only meets a masked dY column, so any IN-IMAGE pixel does -- but it is multiplied by that zero, so it has to
+            // be a pixel of the tensor: with W == 2 the pair's own first column is column -1, which for row 0 of image 0 lies in
+            // front of the tensor, and 0 x whatever a neighbour left there (NaN, Inf) is NaN in every dw of the channel block)
+            const int cm = max(2 * (Ws - 1) - cl, max(cstep * (NP - 1) - 1, 0));
             dl = cl >= Ws ? (cm - cl) * (int)Cin4 : 0;
         } else {
             df = pc == 0 ? (int)Cin4 : 0;                  // column -1 -> 0
