@@ -89,6 +89,70 @@ def _fusion(x, x2, in_scale, in_shift, in_relu, nchw_planar, act=None, stats=Non
     return f
 
 
+def _checked_residual(name, residual, y, what="output"):
+    """The NHWC tensor a kernel's epilogue adds to y (None: none); it must have y's shape."""
+    if residual is not None and tuple(residual.shape) != tuple(y.shape):
+        raise _lib.DvsError("%s: residual shape %s != %s shape %s" % (name, tuple(residual.shape), what, tuple(y.shape)))
+    return None if residual is None else _nhwc(residual)
+
+
+def _sink_or_zeros(name, dw_out, weight_shape, device, pooled, planar=False):
+    """What a weight-gradient kernel accumulates into: the gradient sink dw_out, else a zero-filled [Cout][kh][kw][Cin]-stored
+    tensor of the weight's shape (planar: conv1's [Cout][Cin][kh][8] pack, which no sink can take)."""
+    if dw_out is not None:
+        if planar or tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
+            raise _lib.DvsError("%s: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape" % name)
+        return dw_out
+    if planar:
+        return zeropool.zeros(tuple(weight_shape[:3]) + (8,), device, pooled=pooled)
+    return zeropool.zeros(tuple(weight_shape), device, channels_last=True, pooled=pooled)
+
+
+def _gather_geometry(name, x, x2, k):
+    """Operands of the general gather, x2: None, UPSAMPLE_ONLY or the skip tensor (x is then the half-resolution operand):
+    (x, skip or None, up, B, c1, c2, H, W) with NHWC layouts; the sources must make the k input channels at H x W."""
+    x = _nhwc(x)
+    up = x2 is not None
+    skip = _nhwc(x2) if isinstance(x2, torch.Tensor) else None
+    B, c1, hs, ws = x.shape
+    H, W = (2 * hs, 2 * ws) if up else (hs, ws)
+    c2 = skip.shape[1] if skip is not None else 0
+    if c1 + c2 != k or (skip is not None and tuple(skip.shape) != (B, c2, H, W)):
+        raise _lib.DvsError("%s: operands %s / %s do not make the %d input channels at %dx%d"
+                            % (name, tuple(x.shape), None if skip is None else tuple(skip.shape), k, H, W))
+    return x, skip, up, B, c1, c2, H, W
+
+
+def _plain_operands(name, x, weight, flip, residual, operand):
+    """Checked operands of the stride-1 / pad-1 3x3 kernels: (x, the weight's operand(w, weight, flip), empty y, residual, x's
+    shape, output channels); flip: the data gradient, which maps Cout channels to Cin."""
+    x = _nhwc(x)
+    n, k = weight.shape[:2][::-1] if flip else weight.shape[:2]
+    if x.shape[1] != k:
+        raise _lib.DvsError("%s: input has %d channels, the operand expects %d" % (name, x.shape[1], k))
+    y = torch.empty((x.shape[0], n) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32, memory_format=CL)
+    return x, operand(_nhwc(weight), weight, flip), y, _checked_residual(name, residual, y), tuple(x.shape), n
+
+
+def _wgrad_gen_operands(name, x, x2, dy, weight_shape, dw_out, pooled, y_out, act, want_bias, db_out):
+    """Checked operands of the general-gather weight gradients: _gather_geometry's tuple + (dy, pointer of the forward output or
+    None, activation code, dw, db) -- dw / db are the sinks or zero-filled tensors."""
+    dy = _nhwc(dy)
+    co, ci = weight_shape[:2]
+    geo = _gather_geometry(name, x, x2, ci)
+    B, H, W = geo[3], geo[6], geo[7]
+    if tuple(dy.shape) != (B, co, H, W):
+        raise _lib.DvsError("%s: dy %s does not fit a %s weight at %dx%d" % (name, tuple(dy.shape), tuple(weight_shape), H, W))
+    dact = ACT[act]
+    if (want_bias or db_out is not None) and not dact:
+        raise _lib.DvsError("%s: the bias gradient rides on the activation-derivative path" % name)
+    if dact and (y_out is None or tuple(y_out.shape) != tuple(dy.shape)):
+        raise _lib.DvsError("%s: the activation derivative needs the forward output" % name)
+    dw = _sink_or_zeros(name, dw_out, weight_shape, dy.device, pooled)
+    db = db_out if db_out is not None else (zeropool.zeros((co,), dy.device, pooled=pooled) if want_bias else None)
+    return geo + (dy, _nhwc(y_out).data_ptr() if dact else None, dact, dw, db)
+
+
 def _pack_planar_weight(weight):
     """Encoder conv1: [Cout][Cin][kh][8] with kw zero-padded to 8 (K order (ci,ky,kx))."""
     return torch.nn.functional.pad(weight.contiguous(), (0, 8 - weight.shape[3]))
@@ -106,17 +170,61 @@ def conv2d_forward(x, weight, bias=None, stride=1, pad=0, reflect=False, act=Non
     d = _desc(B, Cin, H, W, weight.shape, stride, pad, reflect)
     Ho, Wo = out_hw(H, W, d.kh, d.kw, stride, pad)
     y = torch.empty((B, d.Cout, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=CL)
-    if residual is not None:
-        residual = _nhwc(residual)
-        if tuple(residual.shape) != tuple(y.shape):
-            raise _lib.DvsError("conv2d_forward: residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    residual = _checked_residual("conv2d_forward", residual, y)
     f = _fusion(x, x2, in_scale, in_shift, in_relu, nchw_planar, act, stats, stat_groups, residual, stat_slots)
     check(_lib.lib().dvs_conv2d_fwd(x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(), C.byref(d), C.byref(f),
                                     _lib.stream()), "dvs_conv2d_fwd")
     return y
 
 
-_prepacked = {}     # weight.data_ptr() -> (packed tensor, weight._version it was packed at, shape, weakref to the weight)
+class _OperandCache(dict):
+    """Kernel operands made from a convolution weight: weight.data_ptr() -> [operand, flipped operand (the data gradient's),
+    stamp, shape, weak reference to the weight].  Keyed by the WEIGHT's own address (the allocator hands a temporary NHWC
+    copy's out again) and pinned to the weight OBJECT: a parameter whose storage moved (an arena, .to()) leaves its address to
+    others, a freed arena's goes to the next arena.  An entry is current while stamp(weight) and the shape are unchanged."""
+
+    def __init__(self, stamp):
+        super().__init__()
+        self.stamp = stamp
+
+    def current(self, weight):
+        """The weight's entry when it may be served, else None."""
+        ent = dict.get(self, weight.data_ptr())
+        ok = ent is not None and ent[4]() is weight and ent[2] == self.stamp(weight) and ent[3] == tuple(weight.shape)
+        return ent if ok else None
+
+    def register(self, weight, op=None, op_flip=None):
+        if len(self) > 1024:
+            for k in [k for k, e in self.items() if e[4]() is None]:
+                del self[k]
+        ent = self[weight.data_ptr()] = [op, op_flip, self.stamp(weight), tuple(weight.shape), weakref.ref(weight)]
+        return ent
+
+    def operand(self, weight, slot, make):
+        """Operand `slot` (0, or 1: the flipped one) of `weight`: made by make() and kept until the weight changes."""
+        ent = self.current(weight) or self.register(weight)
+        if ent[slot] is None:
+            ent[slot] = make()
+        return ent[slot]
+
+    def drop_if_owner(self, weight):
+        """Drop the entry at the weight's address only if it is this weight's (not a newer owner's at the same, reused address)."""
+        ent = dict.get(self, weight.data_ptr())
+        if ent is not None and ent[4]() is weight:
+            del self[weight.data_ptr()]
+
+
+def _p16_stamp(weight):
+    """torch's version counter AND the package's generation counter, which dp.FusedAdam and the other raw-pointer writers bump
+    (nn_ops.bump_generation) when they change weights behind torch's back: a bf16 pack never outlives an optimiser step."""
+    from . import nn_ops
+    return (weight._version, nn_ops.generation())
+
+
+# [Cin][kh][kw][Cout] data-gradient packs: only PackedWeights.repack registers them, on-the-fly packs are not kept
+_prepacked = _OperandCache(lambda weight: weight._version)
+_wino_packed = _OperandCache(lambda weight: weight._version)    # G g G^T operands of the Winograd kernels (either may be None)
+_p16_packed = _OperandCache(_p16_stamp)                         # bf16 operands of the patch kernels
 
 
 def conv2d_dgrad_padded(dz, weight, x_shape, split_c1=0, wino=False, p16=False, y_out=None, act=None):
@@ -182,29 +290,25 @@ class PackedWeights:
         check(_lib.lib().dvs_conv2d_pack_wt_batch(self.table.data_ptr(), len(self.weights), self.total_wgs, _lib.stream()),
               "dvs_conv2d_pack_wt_batch")
         for w, wt in zip(self.weights, self.packs):
-            # the weak reference pins the entry to THIS tensor object: the caching allocator hands the address of a freed
-            # arena to the next one, and a pack of the old network must never serve the new network's data gradient
-            _prepacked[w.data_ptr()] = (wt, w._version, tuple(w.shape), weakref.ref(w))
+            _prepacked.register(w, wt)
         if self.wino_table is not None:
             check(_lib.lib().dvs_wino_weights_batch(self.wino_table.data_ptr(), len(self.wino), self.wino_wgs, _lib.stream()),
                   "dvs_wino_weights_batch")
             for w, (u, uf) in zip(self.wino, self.wino_ops):
-                _wino_packed[w.data_ptr()] = [u, uf, w._version, tuple(w.shape), weakref.ref(w)]
+                _wino_packed.register(w, u, uf)
 
     def release(self):
         """Drop this pack's entries -- only its own: a late-collected owner (trainer / optimiser __del__) must not evict what a
         newer owner has registered at the same, reused arena address (its entries are pinned to ITS weight objects)."""
         for w in self.weights:
-            for table in (_prepacked, _wino_packed):
-                ent = table.get(w.data_ptr())
-                if ent is not None and ent[-1]() is w:
-                    table.pop(w.data_ptr(), None)
+            _prepacked.drop_if_owner(w)
+            _wino_packed.drop_if_owner(w)
 
 
 def _packed_weight(w, weight):
     """[Cin][kh][kw][Cout] operand of the data gradient: the optimiser's pre-packed copy when it is current, else packed here."""
-    ent = _prepacked.get(w.data_ptr())
-    if ent is not None and ent[3]() is weight and ent[1] == weight._version and ent[2] == tuple(weight.shape):
+    ent = _prepacked.current(weight)
+    if ent is not None:
         return ent[0]
     Cout, Cin, kh, kw = weight.shape
     wt = torch.empty(Cin * kh * kw * Cout, device=w.device, dtype=torch.float32)
@@ -217,22 +321,42 @@ _WINO = os.environ.get("DVS_WINOGRAD", "1") != "0"
 _WINO_FORCE = os.environ.get("DVS_WINOGRAD", "1") == "force"       # take the Winograd kernels whatever the cost model says (tests)
 
 
-def _wino_on():
+def _shape(t):
+    """A tensor's shape, or the shape itself: the route predicates read nothing else, so the planners hand them shapes."""
+    return t if isinstance(t, tuple) else tuple(t.shape)
+
+
+def _skip_channels(x2):            # x2: None, UPSAMPLE_ONLY, the skip tensor or its shape
+    return 0 if x2 is None or x2 is UPSAMPLE_ONLY else _shape(x2)[1]
+
+
+def _conv3x3_s1(w_shape, stride, pad, planar, scale):
+    """What every fast path asks first: 3x3, stride 1, pad 1 (zero or reflection), NHWC input without a fused input transform."""
+    return w_shape[2] == 3 and w_shape[3] == 3 and stride == 1 and pad == 1 and not planar and scale is None
+
+
+def _fits32(pixels, w_shape):
+    """The fast kernels' 32-bit buffer offsets: `pixels` rows of the wider of the two channel counts stay below 2 GiB."""
+    return pixels * max(w_shape[0], w_shape[1]) * 4 < 2 ** 31
+
+
+def _bf16(precision=None):        # None: the mode that is set now (_lib.set_precision)
+    return (precision or _lib._precision) == "bf16"
+
+
+def _wino_on(precision=None):
     """The Winograd kernels are fp32 kernels: in the bf16 mode (_lib.set_precision) the direct kernels on the bf16 matrix cores
     are faster than 2.25x fewer fp32 multiplies, so every 3x3 layer takes those."""
-    return _WINO and _lib._precision != "bf16"
+    return _WINO and not _bf16(precision)
 
 
-_wino_packed = {}   # weight.data_ptr() -> [u, u_flip, weight._version, shape, weakref]  (either operand may be None)
-
-
-def wino_eligible(weight, stride, pad, reflect, act, x2, planar, scale):
+def wino_eligible(weight, stride, pad, reflect, act, x2, planar, scale, precision=None):
     """Forward AND data gradient of this convolution run on the Winograd kernel: 3x3, stride 1, zero pad 1, no fused input
     transform or activation, both channel counts multiples of 16 (the kernels' K chunking) and wide enough to fill the
     32-channel MFMA columns."""
-    co, ci, kh, kw = weight.shape
-    return (_wino_on() and kh == 3 and kw == 3 and stride == 1 and pad == 1 and not reflect and act is None and x2 is None
-            and not planar and scale is None and ci % 16 == 0 and co % 16 == 0 and ci >= 64 and co >= 64)
+    ws = _shape(weight)
+    return (_wino_on(precision) and _conv3x3_s1(ws, stride, pad, planar, scale) and not reflect and act is None
+            and x2 is None and ws[1] % 16 == 0 and ws[0] % 16 == 0 and ws[1] >= 64 and ws[0] >= 64)
 
 
 def wino_pays(B, H, W, k, n):
@@ -257,110 +381,65 @@ def _wino_alloc(weight):
 def _wino_weight(w, weight, flip):
     """G g G^T operand of the Winograd kernel ([K][4][N][4]; flip: the data gradient's rotated / transposed filter): the
     optimiser's pre-transformed copy when it is current, else transformed here and kept until the weight changes."""
-    # keyed by the WEIGHT's own address (w may be a temporary NHWC copy whose address the allocator hands out again) and
-    # pinned to the weight OBJECT: a live parameter whose storage moved (an arena, .to()) leaves its old address to others
-    ent = _wino_packed.get(weight.data_ptr())
-    if not (ent is not None and ent[4]() is weight and ent[2] == weight._version and ent[3] == tuple(weight.shape)):
-        if len(_wino_packed) > 1024:
-            for k in [k for k, e in _wino_packed.items() if e[4]() is None]:
-                del _wino_packed[k]
-        ent = [None, None, weight._version, tuple(weight.shape), weakref.ref(weight)]
-        _wino_packed[weight.data_ptr()] = ent
-    if ent[int(flip)] is None:
+    def make():
         u = _wino_alloc(weight)
         check(_lib.lib().dvs_wino_weights(w.data_ptr(), u.data_ptr(), weight.shape[0], weight.shape[1], int(flip), _lib.stream()),
               "dvs_wino_weights")
-        ent[int(flip)] = u
-    return ent[int(flip)]
+        return u
+    return _wino_packed.operand(weight, int(flip), make)
 
 
 # ---- bf16 mode: the same layers on the patch kernel (csrc/conv_p16.hip) -------------------------------------------------------
 _P16 = os.environ.get("DVS_BF16_PATCH", "1") != "0"
-_p16_packed = {}    # weight.data_ptr() -> [pack, pack_flip, weight._version, shape, weakref]
 
 
-def p16_eligible(weight, stride, pad, reflect, act, x2, planar, scale):
+def p16_eligible(weight, stride, pad, reflect, act, x2, planar, scale, precision=None):
     """bf16 mode only: forward AND data gradient of this convolution run on the patch kernel -- 3x3, stride 1, zero pad 1, no
     fused input transform / bias / activation, channel counts multiples of 64."""
-    co, ci, kh, kw = weight.shape
-    return (_P16 and _lib._precision == "bf16" and kh == 3 and kw == 3 and stride == 1 and pad == 1 and not reflect and act is None
-            and x2 is None and not planar and scale is None and ci % 64 == 0 and co % 64 == 0)
+    ws = _shape(weight)
+    return (_P16 and _bf16(precision) and _conv3x3_s1(ws, stride, pad, planar, scale) and not reflect and act is None
+            and x2 is None and ws[1] % 64 == 0 and ws[0] % 64 == 0)
 
 
 def _p16_weight(w, weight, flip):
     """bf16 [9][K/16][N][16] operand of the patch kernel (flip: the data gradient's), kept until the weight changes (same keying
     as _wino_weight)."""
-    # (torch's version counter AND the package's generation counter: dp.FusedAdam and the other raw-pointer writers change the
-    # weights behind torch's back and bump the latter -- nn_ops.bump_generation -- so a pack never outlives an optimiser step)
-    from . import nn_ops
-    stamp = (weight._version, nn_ops.generation())
-    ent = _p16_packed.get(weight.data_ptr())
-    if not (ent is not None and ent[4]() is weight and ent[2] == stamp and ent[3] == tuple(weight.shape)):
-        if len(_p16_packed) > 1024:
-            for k in [k for k, e in _p16_packed.items() if e[4]() is None]:
-                del _p16_packed[k]
-        ent = [None, None, stamp, tuple(weight.shape), weakref.ref(weight)]
-        _p16_packed[weight.data_ptr()] = ent
-    if ent[int(flip)] is None:
+    def make():
         k, n = (weight.shape[0], weight.shape[1]) if flip else (weight.shape[1], weight.shape[0])
         u = torch.empty(9 * k * ((n + 31) // 32 * 32), device=weight.device, dtype=torch.bfloat16)      # (N padded to 32 columns)
         check(_lib.lib().dvs_conv3x3_bf16_pack(w.data_ptr(), u.data_ptr(), weight.shape[0], weight.shape[1], int(flip), _lib.stream()),
               "dvs_conv3x3_bf16_pack")
-        ent[int(flip)] = u
-    return ent[int(flip)]
+        return u
+    return _p16_packed.operand(weight, int(flip), make)
 
 
 def conv3x3_p16(x, weight, stats=None, stat_groups=0, flip=False, residual=None, stat_slots=1):
     """y = conv3x3(x, weight) (stride 1, zero pad 1) with bf16 operands on the patch kernel; flip: the data gradient of that
     convolution, x = dY [B,Cout,H,W] -> dX [B,Cin,H,W] (+ residual).  `weight` must be the parameter object itself."""
-    x, w = _nhwc(x), _nhwc(weight)
-    co, ci = weight.shape[:2]
-    k, n = (co, ci) if flip else (ci, co)
-    B, cx, H, W = x.shape
-    if cx != k:
-        raise _lib.DvsError("conv3x3_p16: input has %d channels, the operand expects %d" % (cx, k))
-    u = _p16_weight(w, weight, flip)
-    y = torch.empty((B, n, H, W), device=x.device, dtype=torch.float32, memory_format=CL)
-    if residual is not None:
-        residual = _nhwc(residual)
-        if tuple(residual.shape) != tuple(y.shape):
-            raise _lib.DvsError("conv3x3_p16: residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    x, u, y, residual, (B, k, H, W), n = _plain_operands("conv3x3_p16", x, weight, flip, residual, _p16_weight)
     check(_lib.lib().dvs_conv3x3_bf16_fwd(x.data_ptr(), u.data_ptr(), residual.data_ptr() if residual is not None else None, y.data_ptr(),
                                           ptr(stats), stat_groups if stats is not None else 0, int(stat_slots), B, H, W, k, n, int(flip),
                                           _lib.stream()), "dvs_conv3x3_bf16_fwd")
     return y
 
 
-def p16_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale):
+def p16_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale, precision=None):
     """bf16 mode only: the decoder's Conv3x3 layers (ReflectionPad2d(1) + 3x3 [+ ELU], optionally nearest-2x upsample (+ concat) in
     the gather) on the patch kernels: 64-channel chunks for the wide levels, the thin kernel (32 output channels per workgroup,
     chunks of 32 / 16) for the 32- and 16-channel ones."""
-    co, ci, kh, kw = weight.shape
-    if not (_P16 and _lib._precision == "bf16" and kh == 3 and kw == 3 and stride == 1 and pad == 1 and reflect and act in (None, "elu")
-            and not planar and scale is None and co % 16 == 0):
-        return False
-    c1 = x.shape[1]
-    if x2 is None:
-        return c1 == ci and c1 % 16 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2
-    if x2 is UPSAMPLE_ONLY:
-        return c1 == ci and c1 % 16 == 0
-    return c1 % 16 == 0 and x2.shape[1] % 16 == 0 and c1 + x2.shape[1] == ci
+    ws, xs, c2 = _shape(weight), _shape(x), _skip_channels(x2)
+    return (_P16 and _bf16(precision) and _conv3x3_s1(ws, stride, pad, planar, scale) and reflect and act in (None, "elu")
+            and ws[0] % 16 == 0 and xs[1] % 16 == 0 and c2 % 16 == 0 and xs[1] + c2 == ws[1]
+            and (x2 is not None or (xs[2] >= 2 and xs[3] >= 2)))          # ReflectionPad2d(1) needs two rows and columns
 
 
 def conv3x3_p16_gen(x, x2, weight, bias=None, act=None, reflect=True, full=False, flip=False, dact_y=None, dact=None):
     """Patch kernel with the general gather (bf16 operands).  x2: None, UPSAMPLE_ONLY or the skip tensor (x is then the
     half-resolution operand).  full: zero-padded full correlation, output [B, N, H+2, W+2] (with flip: the padded-domain data gradient)."""
-    x, w = _nhwc(x), _nhwc(weight)
+    w = _nhwc(weight)
     co, ci = weight.shape[:2]
     k, n = (co, ci) if flip else (ci, co)
-    up = x2 is not None
-    skip = _nhwc(x2) if isinstance(x2, torch.Tensor) else None
-    B, c1, hs, ws = x.shape
-    H, W = (2 * hs, 2 * ws) if up else (hs, ws)
-    c2 = skip.shape[1] if skip is not None else 0
-    if c1 + c2 != k or (skip is not None and tuple(skip.shape) != (B, c2, H, W)):
-        raise _lib.DvsError("conv3x3_p16_gen: operands %s / %s do not make the %d input channels at %dx%d"
-                            % (tuple(x.shape), None if skip is None else tuple(skip.shape), k, H, W))
+    x, skip, up, B, c1, c2, H, W = _gather_geometry("conv3x3_p16_gen", x, x2, k)
     u = _p16_weight(w, weight, flip)
     Ho, Wo, org = (H + 2, W + 2, 2) if full else (H, W, 1)
     y = torch.empty((B, n, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=CL)
@@ -381,12 +460,7 @@ def conv3x3_p16_wgrad(x, dy, weight_shape, dw_out=None, pooled=False):
     x, dy = _nhwc(x), _nhwc(dy)
     co, ci = weight_shape[:2]
     B, _, H, W = x.shape
-    if dw_out is not None:
-        if tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
-            raise _lib.DvsError("conv3x3_p16_wgrad: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape")
-        dw = dw_out
-    else:
-        dw = zeropool.zeros(tuple(weight_shape), dy.device, channels_last=True, pooled=pooled)
+    dw = _sink_or_zeros("conv3x3_p16_wgrad", dw_out, weight_shape, dy.device, pooled)
     check(_lib.lib().dvs_conv3x3_bf16_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ci, co, _P16_WGS, _lib.stream()),
           "dvs_conv3x3_bf16_wgrad")
     return None if dw_out is not None else dw
@@ -395,31 +469,11 @@ def conv3x3_p16_wgrad(x, dy, weight_shape, dw_out=None, pooled=False):
 def conv3x3_p16_wgrad_gen(x, x2, dy, weight_shape, dw_out=None, pooled=False, y_out=None, act=None, want_bias=False, db_out=None):
     """Weight gradient of ReflectionPad2d(1) + [nearest 2x upsample of x (+ concat with x2)] + 3x3 with bf16 operands on the patch
     kernel (arguments and results as conv3x3_wino_wgrad_gen)."""
-    x, dy = _nhwc(x), _nhwc(dy)
-    co, ci = weight_shape[:2]
-    up = x2 is not None
-    skip = _nhwc(x2) if isinstance(x2, torch.Tensor) else None
-    B, c1, hs, ws = x.shape
-    H, W = (2 * hs, 2 * ws) if up else (hs, ws)
-    c2 = skip.shape[1] if skip is not None else 0
-    if c1 + c2 != ci or tuple(dy.shape) != (B, co, H, W) or (skip is not None and tuple(skip.shape) != (B, c2, H, W)):
-        raise _lib.DvsError("conv3x3_p16_wgrad_gen: operands %s / %s / dy %s do not fit a %s weight at %dx%d"
-                            % (tuple(x.shape), None if skip is None else tuple(skip.shape), tuple(dy.shape), tuple(weight_shape), H, W))
-    dact = ACT[act]
-    if (want_bias or db_out is not None) and not dact:
-        raise _lib.DvsError("conv3x3_p16_wgrad_gen: the bias gradient rides on the activation-derivative path")
-    if dact and (y_out is None or tuple(y_out.shape) != tuple(dy.shape)):
-        raise _lib.DvsError("conv3x3_p16_wgrad_gen: the activation derivative needs the forward output")
-    if dw_out is not None:
-        if tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
-            raise _lib.DvsError("conv3x3_p16_wgrad_gen: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape")
-        dw = dw_out
-    else:
-        dw = zeropool.zeros(tuple(weight_shape), dy.device, channels_last=True, pooled=pooled)
-    db = db_out if db_out is not None else (zeropool.zeros((co,), dy.device, pooled=pooled) if want_bias else None)
-    check(_lib.lib().dvs_conv3x3_bf16_wgrad_gen(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(),
-                                                _nhwc(y_out).data_ptr() if dact else None, dw.data_ptr(), ptr(db), B, H, W, c1, c2, co,
-                                                int(up), 1, dact, _P16_WGS, _lib.stream()), "dvs_conv3x3_bf16_wgrad_gen")
+    x, skip, up, B, c1, c2, H, W, dy, yo, dact, dw, db = _wgrad_gen_operands(
+        "conv3x3_p16_wgrad_gen", x, x2, dy, weight_shape, dw_out, pooled, y_out, act, want_bias, db_out)
+    check(_lib.lib().dvs_conv3x3_bf16_wgrad_gen(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(), yo,
+                                                dw.data_ptr(), ptr(db), B, H, W, c1, c2, weight_shape[0], int(up), 1, dact, _P16_WGS,
+                                                _lib.stream()), "dvs_conv3x3_bf16_wgrad_gen")
     return (None if dw_out is not None else dw), (None if db_out is not None else db)
 
 
@@ -429,18 +483,7 @@ STAT_SLOTS = int(os.environ.get("DVS_WINO_STAT_SLOTS", "16"))     # copies of th
 def conv3x3_wino(x, weight, stats=None, stat_groups=0, flip=False, residual=None, bias=None, relu=False, stat_slots=1):
     """y = [relu](conv3x3(x, weight) [+ bias]) (stride 1, zero pad 1) on the Winograd kernel; flip: the data gradient of that
     convolution, x = dY [B,Cout,H,W] -> dX [B,Cin,H,W].  `weight` must be the parameter object itself (the operand cache is pinned to it)."""
-    x, w = _nhwc(x), _nhwc(weight)
-    co, ci = weight.shape[:2]
-    k, n = (co, ci) if flip else (ci, co)
-    B, cx, H, W = x.shape
-    if cx != k:
-        raise _lib.DvsError("conv3x3_wino: input has %d channels, the operand expects %d" % (cx, k))
-    u = _wino_weight(w, weight, flip)
-    y = torch.empty((B, n, H, W), device=x.device, dtype=torch.float32, memory_format=CL)
-    if residual is not None:
-        residual = _nhwc(residual)
-        if tuple(residual.shape) != tuple(y.shape):
-            raise _lib.DvsError("conv3x3_wino: residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    x, u, y, residual, (B, k, H, W), n = _plain_operands("conv3x3_wino", x, weight, flip, residual, _wino_weight)
     # stat_slots > 1: stats is [stat_slots][G][2][N]; the BatchNorm kernels add the copies up (bn.bn_act)
     check(_lib.lib().dvs_conv3x3_wino_fwd_slots(x.data_ptr(), u.data_ptr(), ptr(bias), residual.data_ptr() if residual is not None else None,
                                                 y.data_ptr(), ptr(stats), stat_groups if stats is not None else 0, int(stat_slots),
@@ -451,35 +494,22 @@ def conv3x3_wino(x, weight, stats=None, stat_groups=0, flip=False, residual=None
 _WINO_DEC = os.environ.get("DVS_WINOGRAD_DECODER", "1") != "0"
 
 
-def wino_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale):
+def wino_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale, precision=None):
     """The decoder's wide Conv3x3 layers (ReflectionPad2d(1) + 3x3, ELU, optionally nearest-2x upsample (+ concat) in the
     gather; model/layers.py:26-41, model/depth_decoder.py:52-62) on the Winograd kernel's general gather."""
-    co, ci, kh, kw = weight.shape
-    if not (_wino_on() and _WINO_DEC and kh == 3 and kw == 3 and stride == 1 and pad == 1 and reflect and act in (None, "elu")
-            and not planar and scale is None and ci % 16 == 0 and co % 16 == 0 and ci >= 64 and co >= 64):
-        return False
-    c1 = x.shape[1]
-    if x2 is None:
-        return c1 == ci and x.shape[2] >= 2 and x.shape[3] >= 2
-    if x2 is UPSAMPLE_ONLY:
-        return c1 == ci
-    return c1 % 8 == 0 and c1 + x2.shape[1] == ci
+    ws, xs, c2 = _shape(weight), _shape(x), _skip_channels(x2)
+    return (_wino_on(precision) and _WINO_DEC and _conv3x3_s1(ws, stride, pad, planar, scale) and reflect and act in (None, "elu")
+            and ws[1] % 16 == 0 and ws[0] % 16 == 0 and ws[1] >= 64 and ws[0] >= 64 and xs[1] + c2 == ws[1]
+            and (c2 == 0 or xs[1] % 8 == 0) and (x2 is not None or (xs[2] >= 2 and xs[3] >= 2)))
 
 
 def conv3x3_wino_gen(x, x2, weight, bias=None, act=None, reflect=True, full=False, flip=False):
     """Winograd kernel with the general gather.  x2: None, UPSAMPLE_ONLY or the skip tensor (x is then the half-resolution
     operand).  full: zero-padded full correlation, output [B, N, H+2, W+2] (with flip: the padded-domain data gradient)."""
-    x, w = _nhwc(x), _nhwc(weight)
+    w = _nhwc(weight)
     co, ci = weight.shape[:2]
     k, n = (co, ci) if flip else (ci, co)
-    up = x2 is not None
-    skip = _nhwc(x2) if isinstance(x2, torch.Tensor) else None
-    B, c1, hs, ws = x.shape
-    H, W = (2 * hs, 2 * ws) if up else (hs, ws)
-    c2 = skip.shape[1] if skip is not None else 0
-    if c1 + c2 != k or (skip is not None and tuple(skip.shape) != (B, c2, H, W)):
-        raise _lib.DvsError("conv3x3_wino_gen: operands %s / %s do not make the %d input channels at %dx%d"
-                            % (tuple(x.shape), None if skip is None else tuple(skip.shape), k, H, W))
+    x, skip, up, B, c1, c2, H, W = _gather_geometry("conv3x3_wino_gen", x, x2, k)
     u = _wino_weight(w, weight, flip)
     Ho, Wo, org = (H + 2, W + 2, 2) if full else (H, W, 1)
     y = torch.empty((B, n, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=CL)
@@ -492,12 +522,13 @@ _WINO_WGRAD = os.environ.get("DVS_WINOGRAD_WGRAD", "1") != "0"
 _WINO_WGS = int(os.environ.get("DVS_WINO_WGRAD_WGS", "0"))
 
 
-def wino_wgrad_eligible(weight_shape, x=None):
+def wino_wgrad_eligible(weight_shape, x=None, precision=None):
     """32-channel blocks, and operands below 1 GiB (the kernel's 32-bit offsets carry two mask bits; x: the forward input, which
     has the output's spatial size for these stride-1 layers) -- larger ones keep the implicit-GEMM weight gradient."""
     co, ci = weight_shape[:2]
-    fits = x is None or (x.numel() // x.shape[1] + x.shape[3] + 1) * max(co, ci) * 4 + 8192 < 2 ** 30
-    return _wino_on() and _WINO_WGRAD and co % 32 == 0 and ci % 32 == 0 and fits
+    xs = None if x is None else _shape(x)
+    fits = xs is None or (xs[0] * xs[2] * xs[3] + xs[3] + 1) * max(co, ci) * 4 + 8192 < 2 ** 30
+    return _wino_on(precision) and _WINO_WGRAD and co % 32 == 0 and ci % 32 == 0 and fits
 
 
 def conv3x3_wino_wgrad(x, dy, weight_shape, dw_out=None, pooled=False):
@@ -506,12 +537,7 @@ def conv3x3_wino_wgrad(x, dy, weight_shape, dw_out=None, pooled=False):
     x, dy = _nhwc(x), _nhwc(dy)
     co, ci = weight_shape[:2]
     B, _, H, W = x.shape
-    if dw_out is not None:
-        if tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
-            raise _lib.DvsError("conv3x3_wino_wgrad: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape")
-        dw = dw_out
-    else:
-        dw = zeropool.zeros(tuple(weight_shape), dy.device, channels_last=True, pooled=pooled)
+    dw = _sink_or_zeros("conv3x3_wino_wgrad", dw_out, weight_shape, dy.device, pooled)
     ws, nws = _wgrad_workspace(B, H, W, ci, co, dy.device)
     check(_lib.lib().dvs_conv3x3_wino_wgrad_ws(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ci, co, _WINO_WGS,
                                                ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad")
@@ -533,15 +559,14 @@ def _wgrad_workspace(B, H, W, ci, co, device):
 _WINO_DEC_WGRAD = os.environ.get("DVS_WINOGRAD_DECODER_WGRAD", "1") != "0"
 
 
-def wino_dec_wgrad_eligible(weight_shape, x, x2):
+def wino_dec_wgrad_eligible(weight_shape, x, x2, precision=None):
     """The decoder's wide Conv3x3 layers (the ones wino_dec_eligible sends to the Winograd forward) whose sources split into
     32-channel blocks: their weight gradient runs on the Winograd kernel's reflect / upsample gathers."""
-    co, ci = weight_shape[:2]
-    c2 = x2.shape[1] if isinstance(x2, torch.Tensor) else 0
+    (co, ci), (B, c1, h, w), c2 = weight_shape[:2], _shape(x), _skip_channels(x2)
     up = 1 if x2 is None else 2
-    return (_wino_on() and _WINO_WGRAD and _WINO_DEC_WGRAD and co % 32 == 0 and x.shape[1] % 32 == 0 and c2 % 32 == 0
-            and x.shape[1] + c2 == ci and x.shape[2] * up >= 2 and x.shape[3] * up >= 2
-            and (x.shape[0] * x.shape[2] * x.shape[3] * up * up + 3 * x.shape[3] * up + 3) * max(co, x.shape[1], c2) * 4 + 8192 < 2 ** 30)
+    return (_wino_on(precision) and _WINO_WGRAD and _WINO_DEC_WGRAD and co % 32 == 0 and c1 % 32 == 0 and c2 % 32 == 0
+            and c1 + c2 == ci and h * up >= 2 and w * up >= 2
+            and (B * h * w * up * up + 3 * w * up + 3) * max(co, c1, c2) * 4 + 8192 < 2 ** 30)
 
 
 def wino_dec_wgrad_pays(B, H, W, k, n):
@@ -557,32 +582,12 @@ def conv3x3_wino_wgrad_gen(x, x2, dy, weight_shape, dw_out=None, pooled=False, y
     "relu": dy is multiplied by act'(y_out) as it is loaded and the bias gradient (want_bias, or the sink db_out) taken on the
     way.  x2: None, UPSAMPLE_ONLY or the skip tensor.  dw_out / db_out: gradient sinks to add into.  Returns (dw, db), None
     where a sink took it."""
-    x, dy = _nhwc(x), _nhwc(dy)
-    co, ci = weight_shape[:2]
-    up = x2 is not None
-    skip = _nhwc(x2) if isinstance(x2, torch.Tensor) else None
-    B, c1, hs, ws = x.shape
-    H, W = (2 * hs, 2 * ws) if up else (hs, ws)
-    c2 = skip.shape[1] if skip is not None else 0
-    if c1 + c2 != ci or tuple(dy.shape) != (B, co, H, W) or (skip is not None and tuple(skip.shape) != (B, c2, H, W)):
-        raise _lib.DvsError("conv3x3_wino_wgrad_gen: operands %s / %s / dy %s do not fit a %s weight at %dx%d"
-                            % (tuple(x.shape), None if skip is None else tuple(skip.shape), tuple(dy.shape), tuple(weight_shape), H, W))
-    dact = ACT[act]
-    if (want_bias or db_out is not None) and not dact:
-        raise _lib.DvsError("conv3x3_wino_wgrad_gen: the bias gradient rides on the activation-derivative path")
-    if dact and (y_out is None or tuple(y_out.shape) != tuple(dy.shape)):
-        raise _lib.DvsError("conv3x3_wino_wgrad_gen: the activation derivative needs the forward output")
-    if dw_out is not None:
-        if tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
-            raise _lib.DvsError("conv3x3_wino_wgrad_gen: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape")
-        dw = dw_out
-    else:
-        dw = zeropool.zeros(tuple(weight_shape), dy.device, channels_last=True, pooled=pooled)
-    db = db_out if db_out is not None else (zeropool.zeros((co,), dy.device, pooled=pooled) if want_bias else None)
-    ws, nws = _wgrad_workspace(B, H, W, max(c1, c2), co, dy.device)
-    check(_lib.lib().dvs_conv3x3_wino_wgrad_gen_ws(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(),
-                                                   _nhwc(y_out).data_ptr() if dact else None, dw.data_ptr(), ptr(db), B, H, W, c1, c2, co,
-                                                   int(up), dact, _WINO_WGS, ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad_gen")
+    x, skip, up, B, c1, c2, H, W, dy, yo, dact, dw, db = _wgrad_gen_operands(
+        "conv3x3_wino_wgrad_gen", x, x2, dy, weight_shape, dw_out, pooled, y_out, act, want_bias, db_out)
+    ws, nws = _wgrad_workspace(B, H, W, max(c1, c2), weight_shape[0], dy.device)
+    check(_lib.lib().dvs_conv3x3_wino_wgrad_gen_ws(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(), yo,
+                                                   dw.data_ptr(), ptr(db), B, H, W, c1, c2, weight_shape[0], int(up), dact, _WINO_WGS,
+                                                   ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad_gen")
     return (None if dw_out is not None else dw), (None if db_out is not None else db)
 
 
@@ -613,10 +618,7 @@ def conv2d_dgrad(dy, weight, x_shape, stride, pad, reflect, y_out=None, act=None
               "dvs_conv2d_dgrad")
         return dx, dskip
     dx = torch.empty((B, Cin, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
-    if residual is not None:
-        residual = _nhwc(residual)
-        if tuple(residual.shape) != tuple(dx.shape):
-            raise _lib.DvsError("conv2d_dgrad: residual shape %s != gradient shape %s" % (tuple(residual.shape), tuple(dx.shape)))
+    residual = _checked_residual("conv2d_dgrad", residual, dx, "gradient")
     check(l.dvs_conv2d_dgrad_res(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), yo, dact, None, 0,
                                  residual.data_ptr() if residual is not None else None, _lib.stream()), "dvs_conv2d_dgrad")
     return dx
@@ -631,18 +633,8 @@ def conv2d_wgrad(x, dy, weight_shape, stride, pad, reflect, want_bias, y_out=Non
     Cout, _, kh, kw = weight_shape
     x, x2, B, Cin, H, W = _geometry(x, tuple(weight_shape), x2, nchw_planar)
     d = _desc(B, Cin, H, W, weight_shape, stride, pad, reflect)
-    if dw_out is not None:
-        if nchw_planar or tuple(dw_out.shape) != tuple(weight_shape) or not dw_out.permute(0, 2, 3, 1).is_contiguous():
-            raise _lib.DvsError("conv2d_wgrad: gradient sink must be a [Cout][kh][kw][Cin]-stored tensor of the weight's shape")
-        dw = dw_out
-    elif nchw_planar:
-        dw = zeropool.zeros((Cout, Cin, kh, 8), dy.device, pooled=pooled)
-    else:
-        dw = zeropool.zeros(tuple(weight_shape), dy.device, channels_last=True, pooled=pooled)
-    if db_out is not None:
-        db = db_out
-    else:
-        db = zeropool.zeros((Cout,), dy.device, pooled=pooled) if want_bias else None
+    dw = _sink_or_zeros("conv2d_wgrad", dw_out, weight_shape, dy.device, pooled, nchw_planar)
+    db = db_out if db_out is not None else (zeropool.zeros((Cout,), dy.device, pooled=pooled) if want_bias else None)
     f = _fusion(x, x2, in_scale, in_shift, in_relu, nchw_planar)
     dact = ACT[act]
     yo = _nhwc(y_out).data_ptr() if dact else None
@@ -663,9 +655,107 @@ _PREACT = os.environ.get("DVS_CONV_PREACT", "1") != "0"
 _PADDED = os.environ.get("DVS_CONV_PADDED_DGRAD", "1") != "0"
 
 
+def _plan_forward(x_shape, x2, weight_shape, opts, has_bias, precision):
+    """(route, stat_slots) of the forward launch; the route ("wino" | "p16" | "p16_gen" | "wino_gen" | "direct") also decides
+    which data- and weight-gradient kernels _plan_backward may choose.  Shapes and flags only -- x2: None, UPSAMPLE_ONLY or the
+    skip's shape; opts: conv2d()'s option tuple."""
+    stride, pad, reflect, act, planar, scale, _, want_stats = opts[:8]
+    groups, cfg = int(want_stats) & 3, (stride, pad, reflect)
+    (co, ci), (B, c1, h, w), up2 = weight_shape[:2], x_shape, 1 if x2 is None else 2
+    # bias + ReLU (PoseNet's decoder, model/posenet_single.py:160-164) ride in the Winograd epilogue; the backward then forms
+    # dZ = dY * [Y > 0] and the bias gradient in one pre-activation pass (dvs_act_bwd), which needs Cout / 4 to divide 256
+    wino_tail = (not has_bias and act is None) or (act == "relu" and not groups and 256 % max(co // 4, 1) == 0)
+    if (wino_tail and wino_eligible(weight_shape, *cfg, None, x2, planar, scale, precision) and c1 == ci
+            and _fits32(B * h * w, weight_shape) and wino_pays(B, h, w, ci, co)):
+        route = "wino"
+    elif (not has_bias and act is None and p16_eligible(weight_shape, *cfg, None, x2, planar, scale, precision) and c1 == ci
+          and _fits32(B * h * w, weight_shape)):
+        route = "p16"
+    elif groups or not _fits32(B * (h + 2) * (w + 2) * up2 * up2, weight_shape):
+        route = "direct"                        # (the general gathers have no statistics epilogue)
+    elif p16_dec_eligible(weight_shape, *cfg, act, x_shape, x2, planar, scale, precision):
+        route = "p16_gen"
+    elif wino_dec_eligible(weight_shape, *cfg, act, x_shape, x2, planar, scale, precision) and wino_pays(B, up2 * h, up2 * w, ci, co):
+        route = "wino_gen"
+    else:
+        route = "direct"
+    # the statistics epilogues end with same-address atomics: spread over STAT_SLOTS copies where the consumer adds them up
+    # (STATS_SLOTTED: the caller takes a [slots][G][2][C] table, nn_ops -> bn.bn_act)
+    slotted = (groups and int(want_stats) & STATS_SLOTTED and STAT_SLOTS > 1 and not planar
+               and (route in ("wino", "p16") or _DIRECT_SLOTS))
+    return route, (STAT_SLOTS if slotted else 1)
+
+
+def _plan_backward(route, x_shape, x2, weight_shape, opts, has_bias, needs, has_dxa, precision, deterministic):
+    """(preact, pre_bias, dgrad, wgrad) of the backward launches, from what forward recorded and the modes as they are at
+    backward time.  needs: ctx.needs_input_grad; has_dxa: a skip path's gradient of x arrived with dy.
+      preact: dZ = dY * act'(Y) is formed once (dvs_act_bwd), the gradient kernels see no activation; pre_bias: with db;
+      dgrad:  None | "wino" | "p16" | "padded_p16" | "padded_wino" | "padded" | "direct"  (padded*: full correlation in the
+              reflection-padded domain on that kernel family, then dvs_reflect_fold);
+      wgrad:  None | "wino" | "p16" | "p16_gen" | "wino_gen" | "direct"."""
+    stride, pad, reflect, act, planar, scale = opts[:6]
+    (co, ci), (B, c1, h, w) = weight_shape[:2], x_shape
+    up, c2, bf16 = x2 is not None, _skip_channels(x2), _bf16(precision)
+    conv3x3 = _conv3x3_s1(weight_shape, stride, pad, planar, scale)
+    # wide decoder layers: form dZ once instead of in both gradient kernels' gathers (the data gradient re-derives it for every
+    # tap and N tile) and take the bias gradient (column sums of dZ) on the way: the weight gradient runs on the LDS-DMA kernel
+    preact = bool(ACT[act]) and (route == "wino" or (_PREACT and reflect and not planar and co >= 64 and (needs[0] or up)
+                                                     and needs[1]))
+    pre_bias = preact and has_bias and needs[2] and 256 % (co // 4) == 0
+    act = None if preact else act
+    dgrad = wgrad = None
+    if needs[0] or (isinstance(x2, tuple) and needs[3]):
+        if planar:
+            raise _lib.DvsError("the planar image input of conv1 has no gradient path")
+        padded = _PADDED and preact and reflect and conv3x3 and co % 32 == 0 and h >= 2
+        if (route == "p16_gen" and bf16 and not preact and (co % 64 != 0 or ci % 64 != 0) and h >= 2 and not has_dxa):
+            # bf16 mode, thin decoder layers (no pre-activation pass): padded-domain gradient on the thin patch kernel with the
+            # activation derivative fused into its staging, then the reflection fold / upsample split
+            dgrad = "padded_p16"
+        elif route == "wino" or (route == "p16" and bf16):
+            dgrad = route
+        elif padded and (up or (h >= 3 and w >= 3)):
+            dgrad = "padded_p16" if route == "p16_gen" and bf16 else "padded_wino" if route == "wino_gen" else "padded"
+        else:
+            dgrad = "direct"
+    if needs[1] or (has_bias and needs[2]):
+        want_b = has_bias and not pre_bias
+        Ho, Wo = out_hw(*((2 * h, 2 * w) if up else (h, w)), weight_shape[2], weight_shape[3], stride, pad)      # dy's
+        # decoder layers (wide ones: activation derivative and bias gradient already taken by the pre-activation pass; thin
+        # ones with 32-channel blocks: both fused into the kernel's dY loads) on the reflect / upsample / concat gathers
+        gen = reflect and conv3x3 and act in (None, "elu", "relu") and (ACT[act] or not want_b)
+        if route == "wino" and wino_wgrad_eligible(weight_shape, x_shape, precision):
+            wgrad = "wino"
+        elif route == "p16" and bf16 and not has_bias and not deterministic:
+            wgrad = "p16"
+        elif (gen and _P16 and bf16 and not deterministic and co % 16 == 0 and c1 % 16 == 0 and c2 % 16 == 0
+              and (c2 == 0 or c1 % 32 == 0) and c1 + c2 == ci and _fits32(B * Ho * Wo, weight_shape)):
+            wgrad = "p16_gen"
+        elif gen and wino_dec_wgrad_eligible(weight_shape, x_shape, x2, precision) and wino_dec_wgrad_pays(B, Ho, Wo, ci, co):
+            wgrad = "wino_gen"
+        else:
+            wgrad = "direct"
+    return preact, pre_bias, dgrad, wgrad
+
+
+def _launch_wgrad(route, x, x2, dy, y, weight_shape, opts, dw_out, db_out, want_bias, pooled):
+    """The weight-gradient launch of _plan_backward's route: (dw, db), None where a sink (dw_out / db_out) took it.  opts: the
+    forward's (stride, pad, reflect, act, planar, scale, shift) with the activation the kernel still has to differentiate."""
+    stride, pad, reflect, act, planar, scale, shift = opts
+    if route == "wino":
+        return conv3x3_wino_wgrad(x, dy, weight_shape, dw_out=dw_out, pooled=pooled), None
+    if route == "p16":
+        return conv3x3_p16_wgrad(x, dy, weight_shape, dw_out=dw_out, pooled=pooled), None
+    if route in ("p16_gen", "wino_gen"):
+        gen = conv3x3_p16_wgrad_gen if route == "p16_gen" else conv3x3_wino_wgrad_gen
+        return gen(x, x2, dy, weight_shape, dw_out=dw_out, pooled=pooled, y_out=y, act=act, want_bias=want_bias, db_out=db_out)
+    return conv2d_wgrad(x, dy, weight_shape, stride, pad, reflect, want_bias, y, act, x2=x2, in_scale=scale, in_shift=shift,
+                        nchw_planar=planar, pooled=pooled, dw_out=dw_out, db_out=db_out)
+
+
 class _Conv2d(torch.autograd.Function):
     """y = act(conv(pad(x [, upsample+concat x2]), w) + b) with the hand-written forward / data-gradient /
-    weight-gradient kernels."""
+    weight-gradient kernels: plan (_plan_forward / _plan_backward), then launch."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, x2, opts):
@@ -673,183 +763,100 @@ class _Conv2d(torch.autograd.Function):
         stride, pad, reflect, act, planar, scale, shift, want_stats = opts[:8]
         passthrough = len(opts) > 8 and opts[8]  # also return x itself: its gradient (a skip path's) meets the data gradient here
         ctx.set_materialize_grads(False)         # no zero-filled "gradient" for the statistics output
-        slots_ok = bool(int(want_stats) & STATS_SLOTTED)   # the caller adds up a [slots][G][2][C] table (nn_ops -> bn.bn_act)
-        want_stats = int(want_stats) & 3
-        groups = int(want_stats)                 # 0: none, 1: [2][C], 2: [2][2][C] (first / second half of the batch)
-        # bias + ReLU (PoseNet's decoder, model/posenet_single.py:160-164) ride in the Winograd epilogue; the backward then forms
-        # dZ = dY * [Y > 0] and the bias gradient in one pre-activation pass (dvs_act_bwd), which needs Cout / 4 to divide 256
-        wino_tail = (bias is None and act is None) or (act == "relu" and not groups and 256 % max(weight.shape[0] // 4, 1) == 0)
-        ctx.wino = (wino_tail and wino_eligible(weight, stride, pad, reflect, None, x2, planar, scale) and x.shape[1] == weight.shape[1]
-                    and x.numel() // x.shape[1] * max(weight.shape[0], weight.shape[1]) * 4 < 2 ** 31      # 32-bit buffer offsets
-                    and wino_pays(x.shape[0], x.shape[2], x.shape[3], weight.shape[1], weight.shape[0]))
-        ctx.p16 = (not ctx.wino and bias is None and act is None and p16_eligible(weight, stride, pad, reflect, None, x2, planar, scale)
-                   and x.shape[1] == weight.shape[1] and x.numel() // x.shape[1] * max(weight.shape[0], weight.shape[1]) * 4 < 2 ** 31)
-        up2 = 2 if x2 is not None else 1
-        ctx.p16_dec = (not ctx.wino and not ctx.p16 and not groups and p16_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale)
-                       and x.shape[0] * (x.shape[2] + 2) * (x.shape[3] + 2) * up2 * up2 * max(weight.shape[0], weight.shape[1]) * 4 < 2 ** 31)
-        ctx.wino_dec = (not ctx.wino and not groups and wino_dec_eligible(weight, stride, pad, reflect, act, x, x2, planar, scale)
-                        and x.shape[0] * (x.shape[2] + 2) * (x.shape[3] + 2) * up2 * up2
-                        * max(weight.shape[0], weight.shape[1]) * 4 < 2 ** 31
-                        and wino_pays(x.shape[0], up2 * x.shape[2], up2 * x.shape[3], weight.shape[1], weight.shape[0]))
-        # the statistics epilogues end with same-address atomics: spread over STAT_SLOTS copies where the consumer adds them up
-        slots = STAT_SLOTS if (groups and slots_ok and STAT_SLOTS > 1 and not planar and (ctx.wino or ctx.p16 or _DIRECT_SLOTS)) else 1
+        groups = int(want_stats) & 3             # 0: none, 1: [2][C], 2: [2][2][C] (first / second half of the batch)
+        x_shape, w_shape, x2_plan = tuple(x.shape), tuple(weight.shape), tuple(x2.shape) if isinstance(x2, torch.Tensor) else x2
+        route, slots = _plan_forward(x_shape, x2_plan, w_shape, opts, bias is not None, _lib._precision)
         if groups:
             shape = (2, weight.shape[0]) if groups == 1 else (groups, 2, weight.shape[0])
             stats = zeropool.zeros(((slots, groups) + shape[-2:]) if slots > 1 else shape, x.device)
         else:
             stats = None
-        if ctx.wino:
+        if route == "wino":
             y = conv3x3_wino(x, weight, stats, groups, bias=bias, relu=act == "relu", stat_slots=slots)
-        elif ctx.p16:
+        elif route == "p16":
             y = conv3x3_p16(x, weight, stats, groups, stat_slots=slots)
-        elif ctx.p16_dec:
+        elif route == "p16_gen":
             y = conv3x3_p16_gen(x, x2, weight, bias, act, reflect=True)
-        elif ctx.wino_dec:
+        elif route == "wino_gen":
             y = conv3x3_wino_gen(x, x2, weight, bias, act, reflect=True)
         else:
             y = conv2d_forward(x, weight, bias, stride, pad, reflect, act, x2=x2, in_scale=scale, in_shift=shift,
                                nchw_planar=planar, stats=stats, stat_groups=max(groups, 1), stat_slots=slots)
-        ctx.opts = opts[:7]
-        ctx.x_shape = tuple(x.shape)
-        ctx.has_bias = bias is not None
+        ctx.plan = (route, x_shape, x2_plan, w_shape, opts[:7], bias is not None)
         ctx.bias_ref = bias                      # only to find its gradient sink in backward
         ctx.weight_ref = weight                  # the object the operand caches (_prepacked, _wino_packed) are pinned to
-        ctx.up_only = x2 is UPSAMPLE_ONLY
-        ctx.save_for_backward(x, weight, None if ctx.up_only else x2, y if ACT[act] else None)
+        ctx.save_for_backward(x, weight, x2 if isinstance(x2, torch.Tensor) else None, y if ACT[act] else None)
         ctx.passthrough = passthrough
-        if passthrough:
-            xa = x.view_as(x)
-            if want_stats:
-                ctx.mark_non_differentiable(stats)
-                return y, stats, xa
-            return y, xa
-        if want_stats:
+        out = (y, stats) if groups else (y,)
+        if groups:
             ctx.mark_non_differentiable(stats)
-            return y, stats
-        return y
+        if passthrough:
+            out += (x.view_as(x),)
+        return out if len(out) > 1 else y
 
     @staticmethod
     def backward(ctx, dy, *more):
         # extra output gradients: (d stats,) and / or (d x_alias,) in the order forward returned them
         dxa = more[-1] if ctx.passthrough and more else None
-        if ctx.passthrough and dy is None:
+        if dy is None:
             return dxa, None, None, None, None
         x, weight, x2, y = ctx.saved_tensors     # (unpacking also runs autograd's in-place modification check)
         weight = ctx.weight_ref                  # same data; the parameter object itself for the cache lookups
-        stride, pad, reflect, act, planar, scale, shift = ctx.opts
-        dx = dx2 = dw = db = None
-        if dy is None:
-            return None, None, None, None, None
-        if ctx.up_only:
+        route, x_shape, x2_plan, w_shape, opts, has_bias = ctx.plan
+        stride, pad, reflect, act, planar, scale, shift = opts
+        if x2_plan is UPSAMPLE_ONLY:
             x2 = UPSAMPLE_ONLY
-        preact = False
-        pre_db = None        # bias gradient already taken by the pre-activation pass (tensor to hand back, or True if sunk)
-        if ACT[act] and (ctx.wino or (_PREACT and reflect and not planar and weight.shape[0] >= 64
-                                      and (ctx.needs_input_grad[0] or x2 is not None) and ctx.needs_input_grad[1])):
-            # wide decoder layers: form dZ = dY * act'(Y) once instead of in both gradient kernels' gathers (the data
-            # gradient re-derives it for every tap and N tile), and take the bias gradient (column sums of dZ) in the same
-            # pass -- the weight gradient then has neither an activation nor a bias path and runs on the LDS-DMA kernel
+        needs = ctx.needs_input_grad
+        preact, pre_bias, dgrad, wgrad = _plan_backward(route, x_shape, x2_plan, w_shape, opts, has_bias, needs, dxa is not None,
+                                                        _lib._precision, _lib.deterministic())
+        dx = dx2 = dw = db = pre_db = None       # pre_db: the pre-activation pass's bias gradient, when it is not sunk
+        if preact:
             dy = _nhwc(dy)
             dz = torch.empty_like(dy)
-            Cout = weight.shape[0]
             db_ptr = None
-            if ctx.has_bias and ctx.needs_input_grad[2] and 256 % (Cout // 4) == 0:
+            if pre_bias:
                 bs = gradsink.target(ctx.bias_ref)
                 if bs is not None:
                     gradsink.note(ctx.bias_ref, gradsink.cur_stream())
-                    db_ptr, pre_db = bs.data_ptr(), True
                 else:
-                    pre_db = zeropool.zeros((Cout,), dy.device, pooled=_has_grad(ctx.bias_ref))
-                    db_ptr = pre_db.data_ptr()
-            check(_lib.lib().dvs_act_bwd(dy.data_ptr(), _nhwc(y).data_ptr(), dz.data_ptr(), dy.numel(), ACT[act], db_ptr, Cout,
+                    bs = pre_db = zeropool.zeros((w_shape[0],), dy.device, pooled=_has_grad(ctx.bias_ref))
+                db_ptr = bs.data_ptr()
+            check(_lib.lib().dvs_act_bwd(dy.data_ptr(), _nhwc(y).data_ptr(), dz.data_ptr(), dy.numel(), ACT[act], db_ptr, w_shape[0],
                                          _lib.stream()), "dvs_act_bwd")
             dy, y, act = dz, None, None
-            preact = True
-        need_x = ctx.needs_input_grad[0] or (isinstance(x2, torch.Tensor) and ctx.needs_input_grad[3])
-        if need_x:
-            if planar:
-                raise _lib.DvsError("the planar image input of conv1 has no gradient path")
-            B = ctx.x_shape[0]
-            padded = (_PADDED and preact and reflect and stride == 1 and pad == 1 and weight.shape[2] == 3
-                      and weight.shape[0] % 32 == 0 and ctx.x_shape[2] >= 2)
-            # bf16 mode, thin decoder layers (no pre-activation pass): padded-domain gradient on the thin patch kernel with the
-            # activation derivative fused into its staging, then the reflection fold / upsample split
-            p16_thin = (ctx.p16_dec and _lib._precision == "bf16" and not preact and reflect and stride == 1 and pad == 1
-                        and (weight.shape[0] % 64 != 0 or weight.shape[1] % 64 != 0) and ctx.x_shape[2] >= 2 and dxa is None)
-            if p16_thin:
-                yk = dict(y_out=y, act=act) if ACT[act] else {}
-                if x2 is None:
-                    dx = conv2d_dgrad_padded(dy, weight, ctx.x_shape, p16=True, **yk)
-                else:
-                    dx, dx2 = conv2d_dgrad_padded(dy, weight, (B, weight.shape[1], 2 * ctx.x_shape[2], 2 * ctx.x_shape[3]),
-                                                  split_c1=ctx.x_shape[1], p16=True, **yk)
-            elif ctx.wino:
-                dx = conv3x3_wino(dy, weight, flip=True, residual=dxa)       # + the skip path's gradient in the epilogue
-                dxa = None
-            elif ctx.p16 and _lib._precision == "bf16":
-                dx = conv3x3_p16(dy, weight, flip=True, residual=dxa)
-                dxa = None
-            elif x2 is None:
-                if padded and ctx.x_shape[2] >= 3 and ctx.x_shape[3] >= 3:
-                    dx = conv2d_dgrad_padded(dy, weight, ctx.x_shape, wino=ctx.wino_dec, p16=ctx.p16_dec and _lib._precision == "bf16")
-                else:
-                    dx = conv2d_dgrad(dy, weight, ctx.x_shape, stride, pad, reflect, y, act, residual=dxa)   # + the other paths' gradient
-                    dxa = None
+        if dgrad is not None:
+            up = x2 is not None
+            # upsample(+concat): the kernels see the full-resolution concatenated input; gradient of the nearest 2x upsample = 2x2
+            # sum, of the concat = channel split, both in the kernel's epilogue (or dvs_reflect_fold): (d coarse, d skip) come back
+            full = (x_shape[0], w_shape[1], 2 * x_shape[2], 2 * x_shape[3]) if up else x_shape
+            split = x_shape[1] if up else 0
+            if dgrad in ("wino", "p16"):
+                dx = (conv3x3_wino if dgrad == "wino" else conv3x3_p16)(dy, weight, flip=True, residual=dxa)
+            elif dgrad != "direct":
+                dx = conv2d_dgrad_padded(dy, weight, full, split_c1=split, wino=dgrad == "padded_wino", p16=dgrad == "padded_p16",
+                                         y_out=y, act=act)
+            elif up:
+                dx = conv2d_dgrad(dy, weight, full, stride, pad, reflect, y, act, split_c1=split)
             else:
-                C1, H, W = ctx.x_shape[1], 2 * ctx.x_shape[2], 2 * ctx.x_shape[3]
-                # gradient of the nearest 2x upsample = 2x2 sum; of the concat = channel split: both done in
-                # the data-gradient kernel's epilogue (or, on the padded-domain path, in dvs_reflect_fold)
-                if padded:
-                    dx, dx2 = conv2d_dgrad_padded(dy, weight, (B, weight.shape[1], H, W), split_c1=C1, wino=ctx.wino_dec,
-                                                  p16=ctx.p16_dec and _lib._precision == "bf16")
-                else:
-                    dx, dx2 = conv2d_dgrad(dy, weight, (B, weight.shape[1], H, W), stride, pad, reflect, y, act, split_c1=C1)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            # pool-backed scratch only when autograd will add it into an existing .grad (never adopt it)
+                dx = conv2d_dgrad(dy, weight, full, stride, pad, reflect, y, act, residual=dxa)
+            if up:
+                dx, dx2 = dx
+            elif dgrad in ("wino", "p16", "direct"):
+                dxa = None                       # the skip path's gradient went in with the kernel's epilogue
+        if wgrad is not None:
             wsink = None if planar else gradsink.target(weight)
             bsink = None if planar else gradsink.target(ctx.bias_ref)
+            want_b = has_bias and not pre_bias   # the pre-activation pass may already hold the bias gradient
+            bsink_w = None if pre_bias else bsink
             # fully sunk (nothing goes back to autograd): run beside the data-gradient chain on the side stream
-            want_b = ctx.has_bias and pre_db is None        # the pre-activation pass may already hold the bias gradient
-            if pre_db is not None:
-                bsink_w = None
-            else:
-                bsink_w = bsink
-            side = gradsink.of(ctx).side_stream() if wsink is not None and (bsink is not None or not ctx.has_bias) else None
-            # decoder layer on the Winograd kernels whose activation derivative and bias gradient the pre-activation pass took
-            # decoder layers (wide ones: activation derivative and bias gradient already taken by the pre-activation pass; thin
-            # ones with 32-channel blocks: both fused into the kernel's dY loads) on the Winograd kernel's reflect / upsample gathers
-            wino_gen = (reflect and stride == 1 and pad == 1 and not planar and scale is None and weight.shape[2] == 3
-                        and weight.shape[3] == 3 and act in (None, "elu", "relu") and (ACT[act] or not want_b)
-                        and wino_dec_wgrad_eligible(weight.shape, x, x2)
-                        and wino_dec_wgrad_pays(dy.shape[0], dy.shape[2], dy.shape[3], weight.shape[1], weight.shape[0]))
-            p16_w = ctx.p16 and _lib._precision == "bf16" and not ctx.has_bias and not _lib.deterministic()
-            # bf16 mode: the decoder's layers with 32-channel blocks on the patch kernel's reflect / upsample / concat gather
-            c2w = x2.shape[1] if isinstance(x2, torch.Tensor) else 0
-            p16_gen_w = (_P16 and _lib._precision == "bf16" and not _lib.deterministic() and reflect and stride == 1 and pad == 1
-                         and not planar and scale is None and weight.shape[2] == 3 and weight.shape[3] == 3
-                         and act in (None, "elu", "relu") and (ACT[act] or not want_b) and weight.shape[0] % 16 == 0
-                         and x.shape[1] % 16 == 0 and c2w % 16 == 0 and (c2w == 0 or x.shape[1] % 32 == 0)
-                         and x.shape[1] + c2w == weight.shape[1]
-                         and dy.numel() // dy.shape[1] * max(weight.shape[0], weight.shape[1]) * 4 < 2 ** 31)
+            side = gradsink.of(ctx).side_stream() if wsink is not None and (bsink is not None or not has_bias) else None
+            args = (w_shape, (stride, pad, reflect, act, planar, scale, shift), wsink, bsink_w, want_b, _has_grad(weight))
             if side is None:
                 if wsink is not None or bsink is not None:
                     gradsink.note(weight, gradsink.cur_stream())
                     gradsink.note(ctx.bias_ref, gradsink.cur_stream())
-                if ctx.wino and wino_wgrad_eligible(weight.shape, x):
-                    dw = conv3x3_wino_wgrad(x, dy, tuple(weight.shape), dw_out=wsink, pooled=_has_grad(weight))
-                elif p16_w:
-                    dw = conv3x3_p16_wgrad(x, dy, tuple(weight.shape), dw_out=wsink, pooled=_has_grad(weight))
-                elif p16_gen_w:
-                    dw, db = conv3x3_p16_wgrad_gen(x, x2, dy, tuple(weight.shape), dw_out=wsink, pooled=_has_grad(weight), y_out=y,
-                                                   act=act, want_bias=want_b, db_out=bsink_w)
-                elif wino_gen:
-                    dw, db = conv3x3_wino_wgrad_gen(x, x2, dy, tuple(weight.shape), dw_out=wsink, pooled=_has_grad(weight), y_out=y,
-                                                    act=act, want_bias=want_b, db_out=bsink_w)
-                else:
-                    dw, db = conv2d_wgrad(x, dy, tuple(weight.shape), stride, pad, reflect, want_b, y, act, x2=x2,
-                                          in_scale=scale, in_shift=shift, nchw_planar=planar,
-                                          pooled=_has_grad(weight), dw_out=wsink, db_out=bsink_w)
-                if pre_db is not None and pre_db is not True:
+                dw, db = _launch_wgrad(wgrad, x, x2, dy, y, *args)
+                if pre_db is not None:
                     db = pre_db
             else:
                 cur = gradsink.cur_stream()
@@ -860,19 +867,11 @@ class _Conv2d(torch.autograd.Function):
                 gradsink.note(weight, cur, side)
                 gradsink.note(ctx.bias_ref, cur, side)
                 side.wait_stream(cur)
-                # (the ordered / deterministic forms allocate a workspace inside: those need torch's current stream switched)
-                with (torch.cuda.stream(side) if (_WGRAD_ORDERED or _lib.deterministic()) else _lib.on_stream(side)):
-                    if ctx.wino and wino_wgrad_eligible(weight.shape, x):
-                        conv3x3_wino_wgrad(x, dy, tuple(weight.shape), dw_out=wsink)
-                    elif p16_w:
-                        conv3x3_p16_wgrad(x, dy, tuple(weight.shape), dw_out=wsink)
-                    elif p16_gen_w:
-                        conv3x3_p16_wgrad_gen(x, x2, dy, tuple(weight.shape), dw_out=wsink, y_out=y, act=act, db_out=bsink_w)
-                    elif wino_gen:
-                        conv3x3_wino_wgrad_gen(x, x2, dy, tuple(weight.shape), dw_out=wsink, y_out=y, act=act, db_out=bsink_w)
-                    else:
-                        conv2d_wgrad(x, dy, tuple(weight.shape), stride, pad, reflect, want_b, y, act, x2=x2,
-                                     in_scale=scale, in_shift=shift, dw_out=wsink, db_out=bsink_w)
+                # _lib.on_stream does not switch torch's current stream, so nothing inside may allocate: both gradients go into
+                # sinks; the ordered / deterministic forms (a workspace) take torch.cuda.stream
+                no_alloc = wsink is not None and (not want_b or bsink_w is not None) and not (_WGRAD_ORDERED or _lib.deterministic())
+                with (_lib.on_stream(side) if no_alloc else torch.cuda.stream(side)):
+                    _launch_wgrad(wgrad, x, x2, dy, y, *args)
                 for t in (x, dy, y, x2):
                     if isinstance(t, torch.Tensor):
                         t.record_stream(side)                # keep the allocator from recycling them under the kernel

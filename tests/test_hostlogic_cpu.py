@@ -270,17 +270,41 @@ def test_packed_weights_release_only_their_own_entries():
     old_w, new_w = _W(4096), _W(4096)          # the allocator handed the freed arena's address to the next arena
     pack = DC.PackedWeights.__new__(DC.PackedWeights)
     pack.weights = [old_w]
-    DC._prepacked[4096] = ("pack-of-new", 0, (1,), weakref.ref(new_w))
+    DC._prepacked[4096] = ["pack-of-new", None, 0, (1,), weakref.ref(new_w)]
     DC._wino_packed[4096] = ["u", "uf", 0, (1,), weakref.ref(new_w)]
     try:
         pack.release()
         assert DC._prepacked[4096][0] == "pack-of-new" and DC._wino_packed[4096][0] == "u"
-        DC._prepacked[4096] = ("pack-of-old", 0, (1,), weakref.ref(old_w))
+        DC._prepacked[4096] = ["pack-of-old", None, 0, (1,), weakref.ref(old_w)]
         pack.release()
         assert 4096 not in DC._prepacked and 4096 in DC._wino_packed
     finally:
         DC._prepacked.pop(4096, None)
         DC._wino_packed.pop(4096, None)
+
+
+def test_operand_cache_serves_an_entry_only_while_the_weight_is_unchanged():
+    """conv._OperandCache (behind _prepacked / _wino_packed / _p16_packed): an operand is kept per weight OBJECT until the stamp
+    moves -- torch's version counter, for the bf16 packs also the package's generation counter."""
+    from deep_visual_slam_amd import conv as DC, nn_ops
+    w = torch.zeros(4, 4, 3, 3)
+    make = lambda: object()
+    by_version, by_generation = DC._OperandCache(lambda t: t._version), DC._OperandCache(DC._p16_stamp)
+    for cache in (by_version, by_generation):
+        a, b = cache.operand(w, 0, make), cache.operand(w, 1, make)
+        assert a is not b and cache.operand(w, 0, make) is a and cache.operand(w, 1, make) is b
+        assert cache.current(w.view_as(w)) is None               # same address, another object: not served
+    kept = [c.operand(w, 0, make) for c in (by_version, by_generation)]
+    nn_ops.bump_generation()                                     # a raw-pointer writer changed the weights
+    assert by_version.operand(w, 0, make) is kept[0] and by_generation.operand(w, 0, make) is not kept[1]
+    w.add_(1.0)                                                  # an in-place torch update
+    assert by_version.current(w) is None and by_generation.current(w) is None
+    assert by_version.operand(w, 0, make) is not kept[0]
+    other = torch.zeros(4, 4, 3, 3)
+    by_version.drop_if_owner(other)
+    assert by_version.current(w) is not None
+    by_version.drop_if_owner(w)
+    assert not by_version
 
 
 def test_stream_override_is_scoped_and_nests():

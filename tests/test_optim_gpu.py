@@ -55,7 +55,7 @@ def test_prepacked_dgrad_weights_follow_the_optimiser(gpu_device):
 
     def packed_matches(w):
         ent = DC._prepacked.get(w.data_ptr())
-        assert ent is not None and ent[1] == w._version
+        assert ent is not None and ent[2] == w._version
         co, ci, kh, kw = w.shape
         ref = w.detach().permute(1, 2, 3, 0).contiguous().reshape(-1)       # [Cin][kh][kw][Cout]
         return torch.equal(ent[0], ref)
@@ -75,7 +75,7 @@ def test_prepacked_dgrad_weights_follow_the_optimiser(gpu_device):
     with torch.no_grad():
         net[1].weight.mul_(0.5)
     ent = DC._prepacked[net[1].weight.data_ptr()]
-    assert ent[1] != net[1].weight._version
+    assert ent[2] != net[1].weight._version
     y = DC.conv2d(x, net[0].weight, None, 1, 1).detach().requires_grad_(True)
     cot = torch.randn(2, 32, 12, 16, device=gpu_device)
     (gy,) = torch.autograd.grad(DC.conv2d(y, net[1].weight, None, 1, 1), [y], cot)
