@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstri
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVS_LIB") or os.path.join(HERE, "libdvslam_hip.so")    # DVS_LIB: A/B builds (tools/build_variant.py)
 MAX_SCALES = 4
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _vp = C.c_void_p
 
@@ -62,6 +62,11 @@ class CloudCfg(C.Structure):
     _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("stride_y", C.c_int), ("stride_x", C.c_int),
                 ("from_disp", C.c_int), ("compact", C.c_int), ("k_row_stride", C.c_int),
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float)]
+
+
+class CorrCfg(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("num_levels", C.c_int), ("radius", C.c_int),
+                ("fmap1_nchw", C.c_int), ("fmap2_nchw", C.c_int)]
 
 
 _SIGNATURES = {
@@ -170,6 +175,11 @@ _SIGNATURES = {
     "dvs_cloud_workspace": (C.c_size_t, [C.POINTER(CloudCfg)]),
     "dvs_cloud_fwd": (C.c_int, [C.POINTER(CloudCfg)] + [_vp] * 9),
     "dvs_pose_chain": (C.c_int, [_vp] * 6 + [C.c_int, _vp]),
+    "dvs_corr_sizes": (C.c_int, [C.POINTER(CorrCfg)] + [C.POINTER(C.c_size_t)] * 3),
+    "dvs_corr_build": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 5),
+    "dvs_corr_lookup_fwd": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, _vp, C.c_int, _vp]),
+    "dvs_corr_lookup_bwd": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, C.c_int, _vp, _vp]),
+    "dvs_corr_volume_bwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 7),
 }
 
 _lib = None

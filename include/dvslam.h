@@ -629,6 +629,44 @@ int dvs_cloud_fwd(const dvs_cloud_cfg* cfg, const float* depth_or_disp, const fl
                   float* records, int* count, int* index, void* workspace, void* stream);
 int dvs_pose_chain(const float* T, const float* left, float* world, float* poses, float* M, float* tq, int B, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 10) RAFT correlation block: all-pairs volume, average-pool pyramid, windowed bilinear lookup, and their backward
+ *     replaces model/raft/core/corr.py:12-60 (CorrBlock) with bilinear_sampler, model/raft/core/utils/utils.py:57-71, as
+ *     model/raft/core/raft.py:82-102 uses them (fp32 whatever the autocast state, coordinates detached).
+ *
+ *   N = H * W positions p, q in row-major order; level i has h_i x w_i = (H >> i) x (W >> i) cells, n_i = h_i * w_i.
+ *       V_0[b][p][q] = sum_c fmap1[b][c][p] * fmap2[b][c][q] / sqrt(C)
+ *       V_i[b][p][.] = avg_pool2d(V_{i-1}[b][p][.], 2, stride 2)                                       (corr.py:25-27)
+ *       out[b][i * (2r+1)^2 + a * (2r+1) + e][p] = bilinear sample of V_i[b][p] at (x / 2^i + a - r, y / 2^i + e - r),
+ *           (x, y) = coords[b][0..1][p], pixel coordinates (align_corners), zero padding, floor for negative values.  The x
+ *           offset is the slow index (corr.py:37-43 stacks meshgrid(dy, dx) onto (x, y)).  A coordinate that is not finite, or
+ *           further than r + 2 outside the map, samples nothing: every tap of that pixel and level is 0.
+ *   Pyramid buffer: level i is a contiguous [B * N][n_i] matrix at float offset level_offsets[i]; pyramid_floats in all.
+ *   Feature maps: position-major [B][N][C] (the memory of a channels_last tensor) or, with fmap*_nchw = 1, [B][C][N], which is
+ *       transposed once into the workspace.  C % 4 == 0, 16-byte aligned.  Every level needs >= 2 rows and columns (the
+ *       reference returns NaN below that), N * N < 2^31, num_levels <= 8, radius <= 8.
+ *   The workspace (dvs_corr_sizes, device, 16-byte aligned) is written by dvs_corr_build and must reach dvs_corr_volume_bwd
+ *       unchanged: it holds the pooled rows of fmap2 and the position-major copies.
+ *   dvs_corr_lookup_fwd: out [B][L * (2r+1)^2][N], or out_nhwc = 1: [B][N][L * (2r+1)^2].
+ *   dvs_corr_lookup_bwd: dpyramid (the pyramid's layout) += the gradient of one lookup; the caller zeroes it once and every
+ *       lookup of the block adds into it (one owner per element: no atomics, bit-reproducible).  No gradient for coords
+ *       (raft.py:101 detaches them).
+ *   dvs_corr_volume_bwd: dfmap1, dfmap2 [B][N][C] (overwritten) from the accumulated dpyramid, the pool backward included.
+ *   dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, C, H, W;
+    int num_levels, radius;
+    int fmap1_nchw, fmap2_nchw;      /* 0: [B][N][C] read in place, 1: [B][C][N] */
+} dvs_corr_cfg;
+int dvs_corr_sizes(const dvs_corr_cfg* cfg, size_t* pyramid_floats, size_t* level_offsets, size_t* workspace_bytes);
+int dvs_corr_build(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, float* pyramid, void* workspace, void* stream);
+int dvs_corr_lookup_fwd(const dvs_corr_cfg* cfg, const float* pyramid, const float* coords, float* out, int out_nhwc, void* stream);
+int dvs_corr_lookup_bwd(const dvs_corr_cfg* cfg, const float* coords, const float* dout, int dout_nhwc, float* dpyramid,
+                        void* stream);
+int dvs_corr_volume_bwd(const dvs_corr_cfg* cfg, const float* dpyramid, const float* fmap1, const float* fmap2, void* workspace,
+                        float* dfmap1, float* dfmap2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
