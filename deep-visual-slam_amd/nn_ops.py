@@ -6,6 +6,7 @@ the product: a shape the kernels do not cover raises `DvsError` instead of silen
 (the A/B composition against PyTorch-ROCm's library ops lives in tools/miopen_compose.py, outside the package).
 """
 import os
+import weakref
 
 import torch
 
@@ -69,7 +70,14 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, reflect_pad=0, act=None, x
 # the running statistics), which torch's `_version` counters never see -- so every such writer bumps `_generation`
 # (dp.FusedAdam.step, bn.bn_act / _finalize_groups in training mode) and the cache key includes it.
 _fold_cache = {}
+_fold_owner = {}      # id(weight) -> weak reference to the weight the entry was made for (see folded_bn)
 _generation = 0
+
+
+def _forget_fold(key, ref):
+    if _fold_owner.get(key) is ref:
+        _fold_owner.pop(key, None)
+        _fold_cache.pop(key, None)
 
 
 def bump_generation():
@@ -87,20 +95,25 @@ def folded_bn(weight, bn):
     bn(conv(x, w)) = conv(x, w * s) + (beta - running_mean * s),  s = gamma / sqrt(running_var + eps).
     Cached per weight tensor and refreshed when any of the five tensors is modified -- in place through torch
     (`_version`: torch optimisers, load_state_dict) or through the library's raw-pointer writers (`_generation`) --
-    so an inference loop pays for the fold once."""
+    so an inference loop pays for the fold once.  An entry belongs to the weight OBJECT it was made for and goes when that
+    object dies: id() and the allocator hand a dead weight's identity and address to the next tensor of its size, whose
+    version counters start at the same zeros (a second checkpoint loaded into a fresh network got the first one's fold)."""
     gamma = bn.weight if bn.weight is not None else torch.ones_like(bn.running_var)
     beta = bn.bias if bn.bias is not None else torch.zeros_like(bn.running_var)
     key = id(weight)
     ver = (weight._version, gamma._version, beta._version, bn.running_mean._version, bn.running_var._version,
            weight.data_ptr(), bn.running_mean.data_ptr(), bn.eps, _generation)
     hit = _fold_cache.get(key)
-    if hit is not None and hit[0] == ver:
+    owner = _fold_owner.get(key)
+    if hit is not None and hit[0] == ver and owner is not None and owner() is weight:
         return hit[1], hit[2]
     with torch.no_grad():
         s = gamma / torch.sqrt(bn.running_var + bn.eps)
         w_f = (weight * s.view(-1, 1, 1, 1)).contiguous(memory_format=CL)
         b_f = (beta - bn.running_mean * s).contiguous()
     _fold_cache[key] = (ver, w_f, b_f)
+    if owner is None or owner() is not weight:
+        _fold_owner[key] = weakref.ref(weight, lambda ref, key=key: _forget_fold(key, ref))
     return w_f, b_f
 
 

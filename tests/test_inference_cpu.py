@@ -1,5 +1,6 @@
-"""Host logic of the inference path that needs no GPU: the BatchNorm fold (values, cache invalidation) and the
-disparity-head selection switch."""
+"""Host logic of the inference path that needs no GPU: the BatchNorm fold (values, cache invalidation), the
+disparity-head selection switch, and the case table of the conv epilogue tests (tests/infer_cases.py) tied to the launch
+regimes its rows name."""
 import torch
 import torch.nn.functional as F
 
@@ -28,6 +29,27 @@ def test_folded_bn_equals_eval_batchnorm():
     assert nn_ops.folded_bn(w, bn)[0] is not w_g
 
 
+def test_fold_is_not_inherited_by_the_next_weight_at_the_same_address():
+    """A weight that dies leaves its id() and its storage address to the next tensor of its size, whose version counters start at
+    the same values: the cached fold of the dead weight must not be served for it (within 20 rounds of this loop it was), and
+    the cache must not keep the folds of dead weights."""
+    from deep_visual_slam_amd import nn_ops
+    torch.manual_seed(1)
+    bn = torch.nn.BatchNorm2d(8).eval()
+    bn.running_var.copy_(torch.rand(8) + 0.5)
+    s = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().view(-1, 1, 1, 1)
+    size, reused, seen = len(nn_ops._fold_cache), 0, set()
+    for _ in range(64):
+        w = torch.randn(8, 4, 3, 3).contiguous(memory_format=torch.channels_last)
+        reused += (id(w), w.data_ptr()) in seen
+        seen.add((id(w), w.data_ptr()))
+        w_f, _ = nn_ops.folded_bn(w, bn)
+        assert torch.allclose(w_f, w * s), "the fold of another weight was served"
+        del w, w_f
+    assert len(nn_ops._fold_cache) <= size + 1
+    print("identity and address reused %d times in 64 rounds" % reused)
+
+
 def test_inference_mode_switch():
     from deep_visual_slam_amd import nn_ops
     bn = torch.nn.BatchNorm2d(4)
@@ -37,6 +59,63 @@ def test_inference_mode_switch():
     with torch.no_grad():
         assert nn_ops.inference_mode(bn)
         assert not nn_ops.inference_mode(torch.nn.BatchNorm2d(4, track_running_stats=False).eval())
+
+
+def test_inference_case_table_lands_in_its_regimes():
+    """tests/infer_cases.py: every row of the conv epilogue table gets the launch its columns state and its id names, by the
+    tile / split-K arithmetic restated from csrc/conv_fwd.hip -- a retuned threshold must move the shapes, not hollow the
+    regimes out.  The deterministic mode and the bf16 mode never split."""
+    import infer_cases as IC
+    assert len({r.id for r in IC.ROWS}) == len(IC.ROWS) == 15
+    for r in IC.ROWS:
+        kernel, tile, tiles, ksplit = IC.regime(r)
+        assert (kernel, tile, tiles, ksplit) == (r.kernel, r.tile, r.tiles, r.ksplit), (r.id, kernel, tile, tiles, ksplit)
+        got = dict(kernel=kernel, tile=tile, tiles=tiles, ksplit=ksplit)
+        claims = IC.id_claims(r)
+        assert all(got[k] == v for k, v in claims.items()), (r.id, claims, got)
+        assert IC.regime(r, deterministic=True) == (kernel, tile, tiles, 1)
+        assert IC.regime(r, precision="bf16") == ("planar" if r.planar else "buf", tile, tiles, 1)
+        assert (ksplit > 1) == (kernel == "dma" and tiles < 320 and r.ci // 32 >= 2), r.id
+    by = IC.BY_ID
+    # the regimes the issue names: both sides of each threshold, the ragged last tile, one channel block, a channel tail
+    assert [by[i].ksplit for i in ("l1_split2", "l3_split8", "l4_split16_b3")] == [2, 8, 16]
+    assert by["split_t1024"].tiles == 200 and by["split_t1024"].ksplit == 4          # first tile count aiming at 1024
+    assert IC.launch(IC.rows_m(by["split_t1024"]) - 64, 128, 512, 3)[2:] == (196, 2)  # ... one M tile fewer aims at 256
+    assert by["edge_316"].tiles == 316 and by["edge_320"].tiles == 320 and IC.rows_m(by["edge_320"]) % 64 == 56
+    assert by["tile128"].tiles >= 448 and by["nc1"].ci // 32 == 1 and by["cout96"].co % 128 == 96
+    assert IC.rows_m(by["l1_split2"]) == 117 and all(by[i].ci % 32 for i in ("buf_odd", "buf_48"))
+    # what the table stands for: batch 1 at 480 x 640, BasicBlock convs of layers 1-4
+    full = [IC.launch(480 * 640 // (4 << l) ** 2, c, c, 3)[3] for l, c in enumerate((64, 128, 256, 512))]
+    assert full == [2, 4, 4, 8], full
+    # epilogue combinations: the product's first; seven on the three rows that cover finish, in-kernel DMA and in-kernel staged
+    assert [r.id for r in IC.ROWS if r.all7] == ["l1_split2", "edge_320", "buf_odd"]
+    assert all(len(IC.combos(r)) == (7 if r.all7 else 1) and IC.combos(r)[0] == r.combo for r in IC.ROWS)
+    assert sorted(r.id for r in IC.ROWS if r.bf16) == sorted(["l1_split2", "l3_split8", "edge_320", "buf_48", "s2_entry", "ds_1x1", "stem6"])
+
+
+def test_inference_case_reference_puts_bias_and_residual_inside_the_activation():
+    """The fp64 reference is act(conv + bias + residual); with a unit-scale residual, act(conv + bias) + residual differs on a
+    large share of the elements, so a kernel that applied the ReLU first cannot pass."""
+    import infer_cases as IC
+    r = IC.BY_ID["l1_split2"]
+    x, w, b, res, norm = IC.inputs(r)
+    ref = IC.reference(r, x, w, b, res, norm, (1, 1, 1))
+    pre = F.conv2d(x.double(), w.double(), b.double(), r.s, IC.pad(r))
+    assert torch.allclose(ref, F.relu(pre + res.double()), rtol=0, atol=1e-12)
+    wrong = F.relu(pre) + res.double()
+    assert float(((ref - wrong).abs() > 1e-3 * ref.abs().max()).double().mean()) > 0.3
+    # the bf16 specification rounds x and w only
+    spec = lambda t: t.to(torch.bfloat16).double()
+    ref16 = IC.reference(r, x, w, b, res, norm, (1, 1, 0), spec)
+    assert torch.equal(ref16, F.conv2d(spec(x), spec(w), None, 1, 1) + b.double()[None, :, None, None] + res.double())
+    assert float((ref16 - IC.reference(r, x, w, b, res, norm, (1, 1, 0))).abs().max()) > 1e-3
+    # the stem's dyadic normalisation is exact in fp32 up to its one final rounding
+    s = IC.BY_ID["stem6"]
+    sc, sh = IC.stem_norm(s.ci, True)
+    xs = IC.inputs(s, dyadic=True)[0]
+    prod = xs * sc[None, :, None, None]
+    assert torch.equal(prod.double(), xs.double() * sc.double()[None, :, None, None])
+    assert torch.equal(prod + sh[None, :, None, None], (prod.double() + sh.double()[None, :, None, None]).float())
 
 
 def test_depthnet_scale_selection_is_inference_only():
