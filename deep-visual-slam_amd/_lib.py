@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstri
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVS_LIB") or os.path.join(HERE, "libdvslam_hip.so")    # DVS_LIB: A/B builds (tools/build_variant.py)
 MAX_SCALES = 4
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _vp = C.c_void_p
 
@@ -180,6 +180,11 @@ _SIGNATURES = {
     "dvs_corr_lookup_fwd": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, _vp, C.c_int, _vp]),
     "dvs_corr_lookup_bwd": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, C.c_int, _vp, _vp]),
     "dvs_corr_volume_bwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 7),
+    "dvs_altcorr_sizes": (C.c_int, [C.POINTER(CorrCfg)] + [C.POINTER(C.c_size_t)] * 2),
+    "dvs_altcorr_pool": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 5),
+    "dvs_altcorr_fwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 6 + [C.c_int, _vp]),
+    "dvs_altcorr_bwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 6 + [C.c_int] + [_vp] * 4),
+    "dvs_altcorr_unpool": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -11,10 +11,17 @@
 //   volume bwd  dfmap1 = dV . [fmap2; pools] / sqrt(C),  d[fmap2; pools] = dV^T . fmap1 / sqrt(C), then the average-pool backward
 //               of the pooled rows is added into dfmap2.
 //
+//   on the fly  the alternate form (model/raft/core/corr.py:63-91 over model/raft/alt_cuda_corr/correlation_kernel.cu): no volume.
+//               The (2r+2)^2 patch that the lookup would load from level i is computed from fmap1 and the rows of
+//               [fmap2; pools] instead, then blended as above; its backward sends the patch gradient straight to dfmap1 (one owner
+//               per element) and to d[fmap2; pools] (fp32 atomicAdd: many pixels hit the same row).
+//
 // Layout.  Feature maps are position-major [B][h*w][C] (the memory of a channels_last [B,C,h,w] tensor; contiguous NCHW goes through
 // one transposing pass into the workspace).  Level i of the pyramid is a contiguous [B*h*w][h_i*w_i] matrix at float offset
 // off_i of one buffer; per-sample bases are 64-bit, offsets inside a sample 32-bit (h*w * h*w < 2^31 is required).
-// No float atomics anywhere: every output element has one owner and a fixed summation order, so two runs agree bit for bit.
+// No float atomics anywhere on the all-pairs path: every output element has one owner and a fixed summation order, so two runs
+// agree bit for bit.  The on-the-fly form keeps that for its outputs and for dfmap1; its d[fmap2; pools] is summed with float
+// atomics, so dfmap2 of that form differs in the last bits from run to run.
 // The process-wide precision mode does not reach these kernels (the reference casts to fp32 at raft.py:82-83).
 #include "common.h"
 
@@ -33,7 +40,8 @@ struct Levels {
     long long off[kMaxLevels];      // float offset of level i in the pyramid buffer
 };
 
-int check_cfg(const dvs_corr_cfg* c, const char* who) {
+// volume: the all-pairs form, whose offsets inside a sample are 32-bit; the on-the-fly form has no buffer of that size
+int check_cfg(const dvs_corr_cfg* c, const char* who, bool volume = true) {
     DVS_REQUIRE(c, "%s: null cfg", who);
     DVS_REQUIRE(c->B > 0 && c->C > 0 && c->H > 0 && c->W > 0, "%s: B=%d C=%d H=%d W=%d", who, c->B, c->C, c->H, c->W);
     DVS_REQUIRE(c->C % 4 == 0, "%s: C=%d must be a multiple of 4", who, c->C);
@@ -42,8 +50,10 @@ int check_cfg(const dvs_corr_cfg* c, const char* who) {
     DVS_REQUIRE((c->H >> (c->num_levels - 1)) >= 2 && (c->W >> (c->num_levels - 1)) >= 2,
                 "%s: %dx%d leaves level %d with fewer than 2 rows or columns (the reference divides by W-1: NaN)", who, c->H, c->W,
                 c->num_levels - 1);
-    DVS_REQUIRE((long long)c->H * c->W * c->H * c->W < (1ll << 31), "%s: (H*W)^2 must stay below 2^31", who);
+    DVS_REQUIRE(!volume || (long long)c->H * c->W * c->H * c->W < (1ll << 31), "%s: (H*W)^2 must stay below 2^31", who);
     DVS_REQUIRE((long long)c->B * c->H * c->W * c->C < (1ll << 31), "%s: B*H*W*C must stay below 2^31", who);
+    const long long taps = (long long)c->num_levels * (2 * c->radius + 1) * (2 * c->radius + 1);
+    DVS_REQUIRE(volume || (long long)c->B * taps * c->H * c->W < (1ll << 31), "%s: B*L*(2r+1)^2*H*W must stay below 2^31", who);
     return DVS_OK;
 }
 
@@ -88,6 +98,20 @@ Workspace make_workspace(const dvs_corr_cfg* c, const Levels& lv) {
     return w;
 }
 
+// workspace of the on-the-fly form: [fmap1 position-major, if NCHW][fmap2 position-major, if NCHW]
+struct AltWorkspace {
+    size_t t1, t2, total;
+};
+AltWorkspace make_alt_workspace(const dvs_corr_cfg* c, const Levels& lv) {
+    const size_t fmap = align256((size_t)c->B * lv.N * c->C * sizeof(float));
+    AltWorkspace w;
+    w.t1 = 0;
+    w.t2 = c->fmap1_nchw ? fmap : 0;
+    w.total = w.t2 + (c->fmap2_nchw ? fmap : 0);
+    if (w.total == 0) w.total = 256;
+    return w;
+}
+
 // level of column q and what goes with it: constant indices only, so the table stays in scalar registers
 struct Col {
     int n, rel;         // columns of the level, column inside it
@@ -107,7 +131,8 @@ __device__ __forceinline__ Col column(const Levels& lv, int q) {
 }
 
 // row q of [fmap2; pools] of sample b (q < Q)
-__device__ __forceinline__ const float* cat_row(const Levels& lv, const float* f2, const float* pool, int b, int q) {
+template <typename T>
+__device__ __forceinline__ T* cat_row(const Levels& lv, T* f2, T* pool, int b, int q) {
     return q < lv.N ? f2 + ((size_t)b * lv.N + q) * lv.C : pool + ((size_t)b * (lv.Q - lv.N) + (q - lv.N)) * lv.C;
 }
 
@@ -277,13 +302,53 @@ __device__ __forceinline__ Anchor anchor(const float* __restrict__ coords, int b
     return a;
 }
 
+// patch [kPix][(2r+2)^2 | 1] in LDS -> the (2r+1)^2 taps of every pixel of the tile, channels lvl * (2r+1)^2 + tap of out
+template <bool NHWC>
+__device__ __forceinline__ void blend_patch(const float* patch, const Anchor* anc, float* __restrict__ out, int b, int p0, int N, int lvl,
+                                            int L, int r, int tid) {
+    const int S = 2 * r + 2, SSp = (S * S) | 1, T = 2 * r + 1, TT = T * T, CH = L * TT;
+    for (int idx = tid; idx < kPix * TT; idx += 256) {
+        const int pix = NHWC ? idx / TT : idx % kPix, tap = NHWC ? idx - pix * TT : idx / kPix;
+        const int p = p0 + pix;
+        if (p >= N) continue;
+        const int a = tap / T, bb = tap - a * T;            // a: x offset (the slow index), bb: y offset
+        const float fx = anc[pix].fx, fy = anc[pix].fy;
+        const float* c = patch + pix * SSp + bb * S + a;
+        const float val = c[0] * ((1.f - fx) * (1.f - fy)) + c[1] * (fx * (1.f - fy)) + c[S] * ((1.f - fx) * fy) + c[S + 1] * (fx * fy);
+        const int ch = lvl * TT + tap;
+        if (NHWC) out[((size_t)b * N + p) * CH + ch] = val;
+        else out[((size_t)b * CH + ch) * N + p] = val;
+    }
+}
+
+// gradient of patch cell (u, v) from the <= 4 taps it is a corner of: cell (u, v) is the corner of tap a = u (weight 1 - fx) and
+// of tap a = u - 1 (weight fx); likewise in y.  tap_grad(tap) is dout of tap a * T + bb of this pixel and level.
+template <typename F>
+__device__ __forceinline__ float cell_gradient(int u, int v, int T, float fx, float fy, F tap_grad) {
+    float g = 0.f;
+#pragma unroll
+    for (int da = 0; da < 2; ++da) {
+        const int a = u - da;
+        if (a < 0 || a >= T) continue;
+        const float wx = da ? fx : 1.f - fx;
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            const int bb = v - db;
+            if (bb < 0 || bb >= T) continue;
+            const float wy = db ? fy : 1.f - fy;
+            g += tap_grad(a * T + bb) * (wx * wy);
+        }
+    }
+    return g;
+}
+
 template <bool NHWC>
 __global__ __launch_bounds__(256) void corr_lookup_fwd_kernel(Levels lv, const float* __restrict__ pyr, const float* __restrict__ coords,
                                                               float* __restrict__ out, int r) {
     extern __shared__ float patch[];            // [kPix][SSp]
     __shared__ Anchor anc[kPix];
     const int lvl = blockIdx.y, b = blockIdx.z, p0 = blockIdx.x * kPix, tid = threadIdx.x;
-    const int S = 2 * r + 2, SS = S * S, SSp = SS | 1, T = 2 * r + 1, TT = T * T, CH = lv.L * TT, N = lv.N;
+    const int S = 2 * r + 2, SS = S * S, SSp = SS | 1, N = lv.N;
     int hl = lv.h[0], wl = lv.w[0];
     long long off = lv.off[0];
 #pragma unroll
@@ -305,18 +370,7 @@ __global__ __launch_bounds__(256) void corr_lookup_fwd_kernel(Levels lv, const f
         patch[pix * SSp + cell] = val;
     }
     __syncthreads();
-    for (int idx = tid; idx < kPix * TT; idx += 256) {
-        const int pix = NHWC ? idx / TT : idx % kPix, tap = NHWC ? idx - pix * TT : idx / kPix;
-        const int p = p0 + pix;
-        if (p >= N) continue;
-        const int a = tap / T, bb = tap - a * T;            // a: x offset (the slow index), bb: y offset
-        const float fx = anc[pix].fx, fy = anc[pix].fy;
-        const float* c = patch + pix * SSp + bb * S + a;
-        const float val = c[0] * ((1.f - fx) * (1.f - fy)) + c[1] * (fx * (1.f - fy)) + c[S] * ((1.f - fx) * fy) + c[S + 1] * (fx * fy);
-        const int ch = lvl * TT + tap;
-        if (NHWC) out[((size_t)b * N + p) * CH + ch] = val;
-        else out[((size_t)b * CH + ch) * N + p] = val;
-    }
+    blend_patch<NHWC>(patch, anc, out, b, p0, N, lvl, lv.L, r, tid);
 }
 
 template <bool NHWC>
@@ -352,22 +406,7 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_kernel(Levels lv, const f
         if (!(X >= 0 && X < wl && Y >= 0 && Y < hl)) continue;
         const float fx = anc[pix].fx, fy = anc[pix].fy;
         const float* t = taps + pix * TTp;
-        // cell (u, v) is the corner of tap a = u (weight 1 - fx) and of tap a = u - 1 (weight fx); likewise in y
-        float g = 0.f;
-#pragma unroll
-        for (int da = 0; da < 2; ++da) {
-            const int a = u - da;
-            if (a < 0 || a >= T) continue;
-            const float wx = da ? fx : 1.f - fx;
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const int bb = v - db;
-                if (bb < 0 || bb >= T) continue;
-                const float wy = db ? fy : 1.f - fy;
-                g += t[a * T + bb] * (wx * wy);
-            }
-        }
-        vol[(p0 + pix) * nl + Y * wl + X] += g;
+        vol[(p0 + pix) * nl + Y * wl + X] += cell_gradient(u, v, T, fx, fy, [&](int tap) { return t[tap]; });
     }
 }
 
@@ -479,6 +518,134 @@ __global__ __launch_bounds__(256) void corr_unpool_kernel(Levels lv, const float
     *dst = acc;
 }
 
+// ---- the on-the-fly form ----------------------------------------------------------------------------------------------------------
+// s(p, q) = <fmap1[b][p], cat[b][q]> / sqrt(C) for the cells q of level lvl that the lookup of pixel p touches, and nothing else.
+constexpr int kAltCK = 64;                  // channels of the tile's fmap1 rows in LDS at a time
+constexpr int kAltLd = kAltCK + 4;          // row pitch: 16-byte aligned, and two pixels of one 16-byte read on different banks
+
+struct Level {
+    int h, w, qs;                           // rows, columns, first row of the level in [fmap2; pools]
+};
+__device__ __forceinline__ Level level_of(const Levels& lv, int lvl) {
+    Level g = {lv.h[0], lv.w[0], lv.qs[0]};
+#pragma unroll
+    for (int i = 1; i < kMaxLevels; ++i)
+        if (lvl == i) {
+            g.h = lv.h[i];
+            g.w = lv.w[i];
+            g.qs = lv.qs[i];
+        }
+    return g;
+}
+
+// Forward.  The grid of the lookup (32 pixels x level x sample).  The patch [kPix][(2r+2)^2] is accumulated in LDS over channel
+// chunks of kAltCK: per chunk the tile's fmap1 rows are staged, then every thread owns patch cells (lanes along the cells of a
+// pixel, so the fmap1 reads are broadcasts) and walks the chunk of its row of [fmap2; pools] with 16-byte loads.  A cell outside
+// the map is never loaded and stays 0.  Four partial sums per chunk, the chunks in ascending order: one fixed order, so the
+// output repeats bit for bit.
+template <bool NHWC>
+__global__ __launch_bounds__(256) void altcorr_fwd_kernel(Levels lv, const float* __restrict__ f1, const float* __restrict__ f2,
+                                                          const float* __restrict__ pool, const float* __restrict__ coords,
+                                                          float* __restrict__ out, int r, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float alt_lds[];        // [kPix][kAltLd] fmap1 chunk, [kPix][SSp] patch
+    __shared__ Anchor anc[kPix];
+    float* rows1 = alt_lds;
+    float* patch = alt_lds + kPix * kAltLd;
+    const int lvl = blockIdx.y, b = blockIdx.z, p0 = blockIdx.x * kPix, tid = threadIdx.x;
+    const int S = 2 * r + 2, SS = S * S, SSp = SS | 1, N = lv.N, C = lv.C;
+    const Level g = level_of(lv, lvl);
+    if (tid < kPix) anc[tid] = anchor(coords, b, p0 + tid, N, lvl, g.w, g.h, r);
+    for (int idx = tid; idx < kPix * SSp; idx += 256) patch[idx] = 0.f;
+    for (int k0 = 0; k0 < C; k0 += kAltCK) {
+        const int ck4 = (C - k0 < kAltCK ? C - k0 : kAltCK) / 4;
+        const bool last = k0 + kAltCK >= C;
+        __syncthreads();                    // the previous chunk has been read (first pass: anchors and zeros are in place)
+        for (int i = tid; i < kPix * ck4; i += 256) {
+            const int pix = i / ck4, c4 = i - pix * ck4, p = p0 + pix;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p < N) v = *reinterpret_cast<const float4*>(f1 + ((size_t)b * N + p) * C + k0 + 4 * c4);
+            *reinterpret_cast<float4*>(rows1 + pix * kAltLd + 4 * c4) = v;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < kPix * SS; idx += 256) {
+            const int pix = idx / SS, cell = idx - pix * SS, v = cell / S, u = cell - v * S;
+            const int X = anc[pix].x0 - r + u, Y = anc[pix].y0 - r + v;
+            if (!(X >= 0 && X < g.w && Y >= 0 && Y < g.h)) continue;                              // (a pixel past N has no cell inside)
+            const float4* a = reinterpret_cast<const float4*>(rows1 + pix * kAltLd);
+            const float4* q = reinterpret_cast<const float4*>(cat_row(lv, f2, pool, b, g.qs + Y * g.w + X) + k0);
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+            for (int c4 = 0; c4 < ck4; ++c4) {
+                const float4 x = a[c4], y = q[c4];
+                acc.x = fmaf(x.x, y.x, acc.x);
+                acc.y = fmaf(x.y, y.y, acc.y);
+                acc.z = fmaf(x.z, y.z, acc.z);
+                acc.w = fmaf(x.w, y.w, acc.w);
+            }
+            const float s = patch[pix * SSp + cell] + ((acc.x + acc.y) + (acc.z + acc.w));
+            patch[pix * SSp + cell] = last ? s * scale : s;
+        }
+    }
+    __syncthreads();
+    blend_patch<NHWC>(patch, anc, out, b, p0, N, lvl, lv.L, r, tid);
+}
+
+// Backward.  One workgroup owns 32 pixels of a sample and walks the levels itself, so dfmap1 has one owner per element and a fixed
+// order (bit-reproducible, no atomics): per level the patch gradient g [kPix][(2r+2)^2] is gathered into LDS as the lookup
+// backward does, then thread (pixel, channel), lanes along the channels, runs over the cells inside the map:
+//     dfmap1[p][c]  += g * cat[q][c] / sqrt(C)          (a register; the level's sum is added to the element by its owner)
+//     dcat[q][c]    += g * fmap1[p][c] / sqrt(C)        (fp32 atomicAdd: the windows of many pixels, in many workgroups, share row q)
+// dcat -- dfmap2 and the pooled rows' gradient, zeroed by the caller -- therefore depends on the arrival order in its last bits.
+template <bool NHWC>
+__global__ __launch_bounds__(256) void altcorr_bwd_kernel(Levels lv, const float* __restrict__ f1, const float* __restrict__ f2,
+                                                          const float* __restrict__ pool, const float* __restrict__ coords,
+                                                          const float* __restrict__ dout, float* __restrict__ d1, float* __restrict__ d2,
+                                                          float* __restrict__ dpool, int r, float scale) {
+    extern __shared__ float cellg[];            // [kPix][SSp]
+    __shared__ Anchor anc[kPix];
+    const int b = blockIdx.y, p0 = blockIdx.x * kPix, tid = threadIdx.x;
+    const int S = 2 * r + 2, SS = S * S, SSp = SS | 1, T = 2 * r + 1, TT = T * T, CH = lv.L * TT, N = lv.N, C = lv.C;
+    for (int lvl = 0; lvl < lv.L; ++lvl) {
+        const Level g = level_of(lv, lvl);
+        __syncthreads();                        // the previous level's anchors and cells are no longer read
+        if (tid < kPix) anc[tid] = anchor(coords, b, p0 + tid, N, lvl, g.w, g.h, r);
+        __syncthreads();
+        for (int idx = tid; idx < kPix * SS; idx += 256) {
+            const int pix = NHWC ? idx / SS : idx % kPix, cell = NHWC ? idx - pix * SS : idx / kPix, v = cell / S, u = cell - v * S;
+            const int X = anc[pix].x0 - r + u, Y = anc[pix].y0 - r + v, p = p0 + pix;
+            float val = 0.f;
+            if (X >= 0 && X < g.w && Y >= 0 && Y < g.h)                                           // (a pixel past N has no cell inside)
+                val = cell_gradient(u, v, T, anc[pix].fx, anc[pix].fy, [&](int tap) {
+                    const int ch = lvl * TT + tap;
+                    return NHWC ? dout[((size_t)b * N + p) * CH + ch] : dout[((size_t)b * CH + ch) * N + p];
+                });
+            cellg[pix * SSp + cell] = val;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < kPix * C; idx += 256) {
+            const int pix = idx / C, c = idx - pix * C, p = p0 + pix;
+            if (p >= N) continue;
+            const float fs = f1[((size_t)b * N + p) * C + c] * scale;
+            const int x0 = anc[pix].x0 - r, y0 = anc[pix].y0 - r;
+            float acc = 0.f;
+            for (int v = 0; v < S; ++v) {
+                const int Y = y0 + v;
+                if (Y < 0 || Y >= g.h) continue;
+                for (int u = 0; u < S; ++u) {
+                    const int X = x0 + u;
+                    if (X < 0 || X >= g.w) continue;
+                    const int q = g.qs + Y * g.w + X;
+                    const float gv = cellg[pix * SSp + v * S + u];
+                    acc = fmaf(gv, cat_row(lv, f2, pool, b, q)[c], acc);
+                    atomicAdd(cat_row(lv, d2, dpool, b, q) + c, gv * fs);
+                }
+            }
+            float* o = d1 + ((size_t)b * N + p) * C + c;
+            *o = lvl ? *o + acc * scale : acc * scale;
+        }
+    }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
@@ -579,6 +746,97 @@ int dvs_corr_volume_bwd(const dvs_corr_cfg* cfg, const float* dpyramid, const fl
         hipLaunchKernelGGL(corr_unpool_kernel, dim3((work + 255) / 256, cfg->B), dim3(256), 0, st, lv, dpool, dfmap2);
     }
     return dvs::check_launch("dvs_corr_volume_bwd");
+}
+
+// ---- the on-the-fly form
+int dvs_altcorr_sizes(const dvs_corr_cfg* cfg, size_t* pooled_floats, size_t* workspace_bytes) {
+    if (int rc = check_cfg(cfg, "dvs_altcorr_sizes", false)) return rc;
+    const Levels lv = make_levels(cfg);
+    const size_t pooled = (size_t)cfg->B * (lv.Q - lv.N) * cfg->C;
+    if (pooled_floats) *pooled_floats = pooled ? pooled : 4;            // one level: nothing is pooled, the buffer keeps an address
+    if (workspace_bytes) *workspace_bytes = make_alt_workspace(cfg, lv).total;
+    return DVS_OK;
+}
+
+int dvs_altcorr_pool(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, float* pooled, void* workspace, void* stream) {
+    if (int rc = check_cfg(cfg, "dvs_altcorr_pool", false)) return rc;
+    DVS_REQUIRE(fmap1 && fmap2 && pooled && workspace, "dvs_altcorr_pool: null pointer");
+    DVS_REQUIRE(aligned16(fmap1) && aligned16(fmap2) && aligned16(pooled) && aligned16(workspace), "dvs_altcorr_pool: misaligned pointer");
+    const Levels lv = make_levels(cfg);
+    const AltWorkspace ws = make_alt_workspace(cfg, lv);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(workspace);
+    const float* f2 = fmap2;
+    dim3 tgrid((lv.N + 31) / 32, (cfg->C + 31) / 32, cfg->B);
+    if (cfg->fmap1_nchw)
+        hipLaunchKernelGGL(corr_transpose_kernel, tgrid, dim3(256), 0, st, fmap1, reinterpret_cast<float*>(w + ws.t1), cfg->C, lv.N);
+    if (cfg->fmap2_nchw) {
+        hipLaunchKernelGGL(corr_transpose_kernel, tgrid, dim3(256), 0, st, fmap2, reinterpret_cast<float*>(w + ws.t2), cfg->C, lv.N);
+        f2 = reinterpret_cast<float*>(w + ws.t2);
+    }
+    if (lv.L > 1) {
+        const int work = (lv.Q - lv.N) * (cfg->C / 4);
+        hipLaunchKernelGGL(corr_pool_kernel, dim3((work + 255) / 256, cfg->B), dim3(256), 0, st, lv, f2, pooled);
+    }
+    return dvs::check_launch("dvs_altcorr_pool");
+}
+
+int dvs_altcorr_fwd(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, const float* pooled, const void* workspace,
+                    const float* coords, float* out, int out_nhwc, void* stream) {
+    if (int rc = check_cfg(cfg, "dvs_altcorr_fwd", false)) return rc;
+    DVS_REQUIRE(fmap1 && fmap2 && pooled && workspace && coords && out, "dvs_altcorr_fwd: null pointer");
+    DVS_REQUIRE(aligned16(fmap1) && aligned16(fmap2) && aligned16(pooled) && aligned16(workspace) && aligned4(coords) && aligned4(out),
+                "dvs_altcorr_fwd: misaligned pointer");
+    const Levels lv = make_levels(cfg);
+    const AltWorkspace ws = make_alt_workspace(cfg, lv);
+    const char* w = static_cast<const char*>(workspace);
+    const float* f1 = cfg->fmap1_nchw ? reinterpret_cast<const float*>(w + ws.t1) : fmap1;
+    const float* f2 = cfg->fmap2_nchw ? reinterpret_cast<const float*>(w + ws.t2) : fmap2;
+    const int r = cfg->radius, S = 2 * r + 2;
+    const size_t lds = (size_t)kPix * (kAltLd + ((S * S) | 1)) * sizeof(float);
+    const float scale = (float)(1.0 / std::sqrt((double)cfg->C));
+    dim3 grid((lv.N + kPix - 1) / kPix, lv.L, cfg->B);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (out_nhwc) hipLaunchKernelGGL(altcorr_fwd_kernel<true>, grid, dim3(256), lds, st, lv, f1, f2, pooled, coords, out, r, scale);
+    else hipLaunchKernelGGL(altcorr_fwd_kernel<false>, grid, dim3(256), lds, st, lv, f1, f2, pooled, coords, out, r, scale);
+    return dvs::check_launch("dvs_altcorr_fwd");
+}
+
+int dvs_altcorr_bwd(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, const float* pooled, const void* workspace,
+                    const float* coords, const float* dout, int dout_nhwc, float* dfmap1, float* dfmap2, float* dpooled, void* stream) {
+    if (int rc = check_cfg(cfg, "dvs_altcorr_bwd", false)) return rc;
+    DVS_REQUIRE(fmap1 && fmap2 && pooled && workspace && coords && dout && dfmap1 && dfmap2 && dpooled, "dvs_altcorr_bwd: null pointer");
+    DVS_REQUIRE(aligned16(fmap1) && aligned16(fmap2) && aligned16(pooled) && aligned16(workspace) && aligned4(coords) && aligned4(dout) &&
+                aligned16(dfmap1) && aligned16(dfmap2) && aligned16(dpooled), "dvs_altcorr_bwd: misaligned pointer");
+    const Levels lv = make_levels(cfg);
+    const AltWorkspace ws = make_alt_workspace(cfg, lv);
+    const char* w = static_cast<const char*>(workspace);
+    const float* f1 = cfg->fmap1_nchw ? reinterpret_cast<const float*>(w + ws.t1) : fmap1;
+    const float* f2 = cfg->fmap2_nchw ? reinterpret_cast<const float*>(w + ws.t2) : fmap2;
+    const int r = cfg->radius, S = 2 * r + 2;
+    const size_t lds = (size_t)kPix * ((S * S) | 1) * sizeof(float);
+    const float scale = (float)(1.0 / std::sqrt((double)cfg->C));
+    dim3 grid((lv.N + kPix - 1) / kPix, cfg->B);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dout_nhwc)
+        hipLaunchKernelGGL(altcorr_bwd_kernel<true>, grid, dim3(256), lds, st, lv, f1, f2, pooled, coords, dout, dfmap1, dfmap2, dpooled, r,
+                           scale);
+    else
+        hipLaunchKernelGGL(altcorr_bwd_kernel<false>, grid, dim3(256), lds, st, lv, f1, f2, pooled, coords, dout, dfmap1, dfmap2, dpooled, r,
+                           scale);
+    return dvs::check_launch("dvs_altcorr_bwd");
+}
+
+int dvs_altcorr_unpool(const dvs_corr_cfg* cfg, const float* dpooled, float* dfmap2, void* stream) {
+    if (int rc = check_cfg(cfg, "dvs_altcorr_unpool", false)) return rc;
+    DVS_REQUIRE(dpooled && dfmap2, "dvs_altcorr_unpool: null pointer");
+    DVS_REQUIRE(aligned16(dpooled) && aligned16(dfmap2), "dvs_altcorr_unpool: misaligned pointer");
+    const Levels lv = make_levels(cfg);
+    if (lv.L > 1) {
+        const int work = lv.N * (cfg->C / 4);
+        hipLaunchKernelGGL(corr_unpool_kernel, dim3((work + 255) / 256, cfg->B), dim3(256), 0, static_cast<hipStream_t>(stream), lv, dpooled, dfmap2);
+    }
+    return dvs::check_launch("dvs_altcorr_unpool");
 }
 
 }  // extern "C"

@@ -11,6 +11,12 @@ backward of the N lookups of a block adds into ONE gradient pyramid of the same 
 token that the build node produced, so autograd runs all lookup backwards (each accumulates in place and hands a zero back for
 the token) before the build node's backward, which turns the accumulated gradient into dfmap1 / dfmap2 and frees it.
 Coordinates are constants (raft.py:101 detaches them).  fp32 only, GPU only; the process-wide precision mode has no effect.
+
+AlternateCorrBlock (corr.py:63-91 over alt_cuda_corr) is the same function without the volume: every lookup computes the
+(2r+2)^2 correlations per pixel and level that its taps touch from the feature maps and the pooled rows of fmap2, and its
+backward sends their gradient straight to the feature maps.  Nothing of size (h*w)^2 exists, so there is no (h*w)^2 < 2^31
+limit; a lookup costs more (it re-reads the rows of fmap2 through the caches).  Outputs and dfmap1 repeat bit for bit; dfmap2
+is summed with float atomics and does not.
 """
 import ctypes as C
 
@@ -29,9 +35,14 @@ def _cfg(B, Cn, H, W, num_levels, radius, nchw1=0, nchw2=0):
     return cfg
 
 
-def _check_fmap(name, t):
+class NoCpuPath(DvsError, NotImplementedError):
+    """What AlternateCorrBlock raises for anything that is not a GPU tensor: a DvsError like every input error of this package,
+    and a NotImplementedError because that is what the alternate block of this package answered before it existed."""
+
+
+def _check_fmap(name, t, no_cpu=DvsError):
     if not torch.is_tensor(t) or not t.is_cuda:
-        raise DvsError("%s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
+        raise no_cpu("%s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
     if t.dtype != torch.float32:
         raise DvsError("%s: fp32 only, got %s (the reference casts with .float() at raft.py:82-83 even under autocast)"
                        % (name, t.dtype))
@@ -144,6 +155,21 @@ def _lookup_raw(state, coords, channels_last):
     return out
 
 
+def _check_coords(name, coords, cfg, device):
+    if not torch.is_tensor(coords) or not coords.is_cuda:
+        raise DvsError("%s: GPU coordinates only; this package has no CPU path" % name)
+    if coords.device != device:
+        raise DvsError("%s: coords on %s, the block on %s" % (name, coords.device, device))
+    if coords.requires_grad:
+        raise DvsError("%s: coordinates are constants -- model/raft/core/raft.py:101 detaches them before the lookup "
+                       "(coords1 = coords1.detach()); pass coords.detach()" % name)
+    if tuple(coords.shape) != (cfg.B, 2, cfg.H, cfg.W):
+        raise DvsError("%s: coords must be [%d,2,%d,%d], got %s" % (name, cfg.B, cfg.H, cfg.W, tuple(coords.shape)))
+    if coords.dtype != torch.float32:
+        raise DvsError("%s: fp32 coordinates only, got %s" % (name, coords.dtype))
+    return coords.contiguous()
+
+
 def _memory_format_flag(memory_format):
     if memory_format in (None, torch.contiguous_format):
         return False
@@ -178,18 +204,7 @@ class CorrBlock:
     def __call__(self, coords, memory_format=None):
         st = self._state
         cfg = st.cfg
-        if not torch.is_tensor(coords) or not coords.is_cuda:
-            raise DvsError("CorrBlock: GPU coordinates only; this package has no CPU path")
-        if coords.device != st.pyramid.device:
-            raise DvsError("CorrBlock: coords on %s, the block on %s" % (coords.device, st.pyramid.device))
-        if coords.requires_grad:
-            raise DvsError("CorrBlock: coordinates are constants -- model/raft/core/raft.py:101 detaches them before the lookup "
-                           "(coords1 = coords1.detach()); pass coords.detach()")
-        if tuple(coords.shape) != (cfg.B, 2, cfg.H, cfg.W):
-            raise DvsError("CorrBlock: coords must be [%d,2,%d,%d], got %s" % (cfg.B, cfg.H, cfg.W, tuple(coords.shape)))
-        if coords.dtype != torch.float32:
-            raise DvsError("CorrBlock: fp32 coordinates only, got %s" % coords.dtype)
-        coords = coords.contiguous()
+        coords = _check_coords("CorrBlock", coords, cfg, st.pyramid.device)
         cl = _memory_format_flag(memory_format)
         if self._token.requires_grad and torch.is_grad_enabled():
             st.grad = None                              # left behind only by a backward pass that did not finish
@@ -212,6 +227,120 @@ def corr_pyramid(fmap1, fmap2, num_levels=4, radius=4):
 def corr_lookup(block, coords, memory_format=None):
     """[B, L * (2r+1)^2, h, w] correlation features of `block` at `coords` [B,2,h,w] (x, y)."""
     return block(coords, memory_format=memory_format)
+
+
+# ---- the on-the-fly form ---------------------------------------------------------------------------------------------------
+def _alt_sizes(cfg):
+    """(pooled-row floats, workspace bytes) of dvs_altcorr_sizes, where every limit of the on-the-fly kernels is checked."""
+    floats, ws = C.c_size_t(), C.c_size_t()
+    check(_lib.lib().dvs_altcorr_sizes(C.byref(cfg), C.byref(floats), C.byref(ws)), "dvs_altcorr_sizes")
+    return floats.value, ws.value
+
+
+class _AltState:
+    """What the lookups of one alternate block share: geometry, the memory the kernels read the feature maps from (the
+    tensors themselves when they are channels_last, else layout copies / the workspace's transposed copies)."""
+
+    def __init__(self, cfg, f1, f2, workspace):
+        self.cfg, self.f1, self.f2, self.workspace = cfg, f1, f2, workspace
+
+
+class _AltPool(torch.autograd.Function):
+    """fmap2 -> the pooled rows of levels 1 .. L-1 (and, on the way, the transposed copies of NCHW maps in the workspace)."""
+
+    @staticmethod
+    def forward(ctx, fmap2, state, floats):
+        ctx.set_materialize_grads(False)                # one level: the rows are never read and get no gradient
+        pooled = torch.empty(floats, device=fmap2.device, dtype=torch.float32)
+        check(_lib.lib().dvs_altcorr_pool(C.byref(state.cfg), ptr(state.f1), ptr(state.f2), ptr(pooled), ptr(state.workspace),
+                                          _lib.stream()), "dvs_altcorr_pool")
+        ctx.state = state
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        if dpooled is None:
+            return None, None, None
+        cfg = ctx.state.cfg
+        d2 = torch.zeros(cfg.B, cfg.H * cfg.W, cfg.C, device=dpooled.device, dtype=torch.float32)
+        check(_lib.lib().dvs_altcorr_unpool(C.byref(cfg), ptr(dpooled.contiguous()), ptr(d2), _lib.stream()), "dvs_altcorr_unpool")
+        return d2.view(cfg.B, cfg.H, cfg.W, cfg.C).permute(0, 3, 1, 2), None, None
+
+
+def _alt_lookup_raw(state, pooled, coords, channels_last):
+    cfg = state.cfg
+    ch = cfg.num_levels * (2 * cfg.radius + 1) ** 2
+    out = torch.empty(cfg.B, ch, cfg.H, cfg.W, device=coords.device, dtype=torch.float32,
+                      memory_format=CL if channels_last else torch.contiguous_format)
+    check(_lib.lib().dvs_altcorr_fwd(C.byref(cfg), ptr(state.f1), ptr(state.f2), ptr(pooled), ptr(state.workspace), ptr(coords),
+                                     ptr(out.permute(0, 2, 3, 1) if channels_last else out), int(bool(channels_last)),
+                                     _lib.stream()), "dvs_altcorr_fwd")
+    return out
+
+
+class _AltLookup(torch.autograd.Function):
+    """One lookup.  Its backward returns dfmap1, dfmap2 and the gradient of the pooled rows; autograd sums those of the N
+    lookups of a block, and _AltPool's backward turns the summed pooled-row gradient into the rest of dfmap2."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, pooled, coords, state, channels_last):
+        # saved through autograd, so that an in-place change between forward and backward is an error, not a wrong gradient
+        ctx.save_for_backward(fmap1, fmap2, pooled)
+        ctx.state, ctx.coords = state, coords
+        return _alt_lookup_raw(state, pooled.detach(), coords, channels_last)
+
+    @staticmethod
+    def backward(ctx, dout):
+        st = ctx.state
+        cfg = st.cfg
+        _, _, pooled = ctx.saved_tensors                # (reading them is what checks their versions)
+        nhwc = int(dout.is_contiguous(memory_format=CL) and not dout.is_contiguous())
+        dout = dout.permute(0, 2, 3, 1) if nhwc else dout.contiguous()
+        N = cfg.H * cfg.W
+        d1 = torch.empty(cfg.B, N, cfg.C, device=dout.device, dtype=torch.float32)
+        d2 = torch.zeros(cfg.B, N, cfg.C, device=dout.device, dtype=torch.float32)
+        dpooled = torch.zeros_like(pooled)
+        check(_lib.lib().dvs_altcorr_bwd(C.byref(cfg), ptr(st.f1), ptr(st.f2), ptr(pooled), ptr(st.workspace), ptr(ctx.coords),
+                                         ptr(dout), nhwc, ptr(d1), ptr(d2), ptr(dpooled), _lib.stream()), "dvs_altcorr_bwd")
+        as_map = lambda d: d.view(cfg.B, cfg.H, cfg.W, cfg.C).permute(0, 3, 1, 2)       # [B,C,h,w] in channels_last memory
+        return (as_map(d1) if ctx.needs_input_grad[0] else None, as_map(d2) if ctx.needs_input_grad[1] else None,
+                dpooled if ctx.needs_input_grad[2] and cfg.num_levels > 1 else None, None, None, None)
+
+
+class AlternateCorrBlock:
+    """model/raft/core/corr.py:63-91 (alternate_corr=True), differentiable in both feature maps.  Holds the feature maps and
+    the pooled rows of fmap2 -- (1 + 1/4 + ...) feature maps, not a volume."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        _check_fmap("AlternateCorrBlock: fmap1", fmap1, NoCpuPath)
+        _check_fmap("AlternateCorrBlock: fmap2", fmap2, NoCpuPath)
+        if fmap1.shape != fmap2.shape:
+            raise DvsError("AlternateCorrBlock: fmap1 %s and fmap2 %s differ" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+        if fmap2.device != fmap1.device:
+            raise DvsError("AlternateCorrBlock: fmap1 on %s, fmap2 on %s" % (fmap1.device, fmap2.device))
+        B, Cn, H, W = fmap1.shape
+        self.num_levels, self.radius = int(num_levels), int(radius)
+        _alt_sizes(_cfg(B, Cn, H, W, self.num_levels, self.radius))    # every shape limit, before anything is allocated
+        f1, n1 = _layout(fmap1.detach())
+        f2, n2 = _layout(fmap2.detach())
+        cfg = _cfg(B, Cn, H, W, self.num_levels, self.radius, n1, n2)
+        floats, ws = _alt_sizes(cfg)
+        workspace = torch.empty(ws, device=fmap1.device, dtype=torch.uint8)
+        self._state = _AltState(cfg, f1, f2, workspace)
+        self._fmap1, self._fmap2 = fmap1, fmap2
+        self._pooled = _AltPool.apply(fmap2, self._state, floats)
+
+    def __call__(self, coords, memory_format=None):
+        st = self._state
+        coords = _check_coords("AlternateCorrBlock", coords, st.cfg, self._fmap1.device)
+        return _AltLookup.apply(self._fmap1, self._fmap2, self._pooled, coords, st, _memory_format_flag(memory_format))
+
+
+def altcorr_bytes(B, Cn, H, W, num_levels=4, radius=4):
+    """Bytes an AlternateCorrBlock holds beside its inputs -- the pooled rows of fmap2 -- plus one lookup's output: the
+    counterpart of pyramid_bytes.  (NCHW inputs add one position-major copy of each map, 4 * B * C * H * W bytes.)"""
+    pooled = 4 * B * Cn * sum((H >> i) * (W >> i) for i in range(1, num_levels))
+    return pooled + 4 * B * num_levels * (2 * radius + 1) ** 2 * H * W
 
 
 def pyramid_bytes(B, H, W, num_levels=4):

@@ -667,6 +667,42 @@ int dvs_corr_lookup_bwd(const dvs_corr_cfg* cfg, const float* coords, const floa
 int dvs_corr_volume_bwd(const dvs_corr_cfg* cfg, const float* dpyramid, const float* fmap1, const float* fmap2, void* workspace,
                         float* dfmap1, float* dfmap2, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (ABI 11) RAFT correlation block, on-the-fly form: the lookup without the volume
+ *     replaces AlternateCorrBlock, model/raft/core/corr.py:63-91, and the kernels behind it, model/raft/alt_cuda_corr/; unlike the
+ *     reference's Python, which never wires alt_cuda_corr.backward into autograd, the gradients of both feature maps are here.
+ *
+ *   With N, h_i, w_i, coords and the channel order as above, and f2_i = avg_pool2d applied i times to fmap2 (2 x 2, stride 2):
+ *       s_i(p, q) = sum_c fmap1[b][c][p] * f2_i[b][c][q] / sqrt(C)
+ *       out[b][i * (2r+1)^2 + a * (2r+1) + e][p] = bilinear blend, zero padding, of s_i(p, .) at (x / 2^i + a - r, y / 2^i + e - r)
+ *   Pooling is linear, so this is the function dvs_corr_build + dvs_corr_lookup_fwd compute; only the (2r+2)^2 values s_i(p, q) that
+ *   a pixel's taps touch are formed, inside the lookup, and nothing of size N * N exists.  Non-finite and far-outside coordinates
+ *   give exact zeros as above.
+ *   Same dvs_corr_cfg and limits (C % 4 == 0, num_levels <= 8, radius <= 8, >= 2 rows and columns on every level, B * N * C < 2^31)
+ *       EXCEPT N * N < 2^31, which is replaced by B * L * (2r+1)^2 * N < 2^31.  dvs_altcorr_sizes checks them all.
+ *   pooled: the rows of f2_1 .. f2_{L-1}, [B][n_1 + .. + n_{L-1}][C], pooled_floats floats (4 when L = 1: nothing is stored, the
+ *       buffer only needs an address), 16-byte aligned.  dpooled has the same layout.
+ *   workspace (workspace_bytes, device, 16-byte aligned): the position-major copies of feature maps given as [B][C][N]; written by
+ *       dvs_altcorr_pool, read by dvs_altcorr_fwd and dvs_altcorr_bwd.
+ *   dvs_altcorr_pool:   transposes fmap*_nchw maps into the workspace and writes `pooled`.  Once per pair of feature maps.
+ *   dvs_altcorr_fwd:    out [B][L * (2r+1)^2][N], or out_nhwc = 1: [B][N][L * (2r+1)^2].  Fixed summation order: bit-reproducible.
+ *   dvs_altcorr_bwd:    the gradient of ONE lookup for the cotangent dout (layout as out).
+ *                           dfmap1 [B][N][C] is overwritten; one owner per element and a fixed order: bit-reproducible.
+ *                           dfmap2 [B][N][C] and dpooled are ADDED into with fp32 atomic adds (the windows of many pixels share a
+ *                           row); the caller zeroes them.  Their last bits depend on the arrival order: NOT bit-reproducible.
+ *                       No gradient for coords.
+ *   dvs_altcorr_unpool: dfmap2 [B][N][C] += the average-pool backward of dpooled (one owner per element: bit-reproducible given
+ *                       its input).
+ *   dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_altcorr_sizes(const dvs_corr_cfg* cfg, size_t* pooled_floats, size_t* workspace_bytes);
+int dvs_altcorr_pool(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, float* pooled, void* workspace, void* stream);
+int dvs_altcorr_fwd(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, const float* pooled, const void* workspace,
+                    const float* coords, float* out, int out_nhwc, void* stream);
+int dvs_altcorr_bwd(const dvs_corr_cfg* cfg, const float* fmap1, const float* fmap2, const float* pooled, const void* workspace,
+                    const float* coords, const float* dout, int dout_nhwc, float* dfmap1, float* dfmap2, float* dpooled, void* stream);
+int dvs_altcorr_unpool(const dvs_corr_cfg* cfg, const float* dpooled, float* dfmap2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
