@@ -185,6 +185,10 @@ _SIGNATURES = {
     "dvs_altcorr_fwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 6 + [C.c_int, _vp]),
     "dvs_altcorr_bwd": (C.c_int, [C.POINTER(CorrCfg)] + [_vp] * 6 + [C.c_int] + [_vp] * 4),
     "dvs_altcorr_unpool": (C.c_int, [C.POINTER(CorrCfg), _vp, _vp, _vp]),
+    "dvs_gru_gates_fwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp]),
+    "dvs_gru_blend_fwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp]),
+    "dvs_gru_blend_bwd": (C.c_int, [_vp] * 8 + [C.c_size_t, C.c_int, _vp]),
+    "dvs_gru_gates_bwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp]),
 }
 
 _lib = None

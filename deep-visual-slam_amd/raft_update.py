@@ -1,0 +1,316 @@
+"""SmallRAFT's update block on the device: motion encoder, ConvGRU, flow head (model/raft/core/update.py:62-112).
+
+    raft.update_block = raft_update.SmallUpdateBlock.from_module(raft.update_block)
+    net, _, delta_flow = raft.update_block(net, inp, corr, flow)                    # raft.py:104-105
+
+The reference's ConvGRU convolves ONE 242-channel concatenation hx = cat[h(hd), inp(64), motion(80), flow(2)] three times
+(update.py:23-31).  242 is not a multiple of 4, so none of this package's kernels can gather it -- and they do not have to: a
+convolution is linear in its input channels, conv(W, cat[a, b]) = conv(W[:, A], a) + conv(W[:, B], b).  The block therefore runs
+
+    c   = conv(inp,        cat[Wz, Wr, Wq][:, hd:hd+64]) + cat[bz, br, bq]    once per context (raft.py:95 makes inp once, :100-117
+                                                                              call the block 12 times with it): 26 % of the flops
+    a_x = conv(motion(84), cat[Wz, Wr, Wq][:, hd+64:])                        the 82 motion channels zero-padded to 84
+    a_h = conv(h,          cat[Wz, Wr][:, :hd])
+    z, r, rh = gates(a_h, a_x, c, h)                                          csrc/gru.hip
+    a_q = conv(rh,         Wq[:, :hd])
+    h'  = blend(a_q, a_x, c, z, h)                                            csrc/gru.hip
+
+with every convolution on conv.conv2d / conv.head_conv2d (the route plan picks the kernels, the process-wide precision mode applies)
+and the gate arithmetic on four kernels of its own.  Weights are sliced, concatenated and zero-padded by differentiable torch ops
+once per context, so gradients land on the original parameters, whose names and shapes are the reference's: a raft-small.pth
+sub-dictionary loads with load_state_dict.  GPU and fp32 only; no host synchronisation in forward or backward.
+"""
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, conv, nn_ops
+from ._lib import DvsError, check
+
+CL = torch.channels_last
+CTX_DIM = 64            # channels of `inp` (SmallRAFT's context_dim, raft.py:34)
+MOTION_DIM = 82         # SmallMotionEncoder's 80 + the 2 flow channels (update.py:77)
+
+_ENCODER = (("convc1", 96, None, 1), ("convf1", 64, 2, 7), ("convf2", 32, 64, 3), ("conv", 80, 128, 3))
+
+
+def _rows(t):
+    """(P, channels) of a [B,C,H,W] tensor in channels_last memory: the [P][C] matrix the gate kernels see."""
+    B, Cn, H, W = t.shape
+    return B * H * W, Cn
+
+
+def _as_map(m, like, channels):
+    """A [B,H,W,channels] matrix buffer as the [B,channels,H,W] channels_last tensor autograd expects."""
+    B, _, H, W = like.shape
+    return m.view(B, H, W, channels).permute(0, 3, 1, 2)
+
+
+def _empty_map(like, channels):
+    B, _, H, W = like.shape
+    return torch.empty((B, H, W, channels), device=like.device, dtype=torch.float32)
+
+
+def _gates_raw(a_h, a_x, c, h):
+    P, hd = _rows(h)
+    z, r, rh = (_as_map(_empty_map(h, hd), h, hd) for _ in range(3))
+    check(_lib.lib().dvs_gru_gates_fwd(a_h.data_ptr(), a_x.data_ptr(), c.data_ptr(), h.data_ptr(), z.data_ptr(), r.data_ptr(),
+                                       rh.data_ptr(), P, hd, _lib.stream()), "dvs_gru_gates_fwd")
+    return z, r, rh
+
+
+def _blend_raw(a_q, a_x, c, z, h):
+    P, hd = _rows(h)
+    q, h_new = (_as_map(_empty_map(h, hd), h, hd) for _ in range(2))
+    check(_lib.lib().dvs_gru_blend_fwd(a_q.data_ptr(), a_x.data_ptr(), c.data_ptr(), z.data_ptr(), h.data_ptr(), q.data_ptr(),
+                                       h_new.data_ptr(), P, hd, _lib.stream()), "dvs_gru_blend_fwd")
+    return q, h_new
+
+
+class _Link:
+    """What the blend node's backward leaves for the gates node's of the same step: dpre [P][3hd] and dah [P][2hd] with the z
+    (and q) columns written, and dh_a.  The gates node consumes z, which the blend node reads, so autograd always runs the blend
+    node's backward first; the gates node then fills the r columns and hands the finished matrices on.  That way dpre is written
+    once and is the gradient of a_x and of c without a sum of two half-empty tensors, and dh = dh_a + d_rh * r costs no
+    accumulation pass."""
+    __slots__ = ("dpre", "dah", "dh_a")
+
+    def __init__(self):
+        self.dpre = self.dah = self.dh_a = None
+
+
+class _Gates(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a_h, a_x, c, h, link):
+        ctx.set_materialize_grads(False)
+        a_h, a_x, c, h = (conv._nhwc(t.detach()) for t in (a_h, a_x, c, h))
+        z, r, rh = _gates_raw(a_h, a_x, c, h)
+        ctx.save_for_backward(r, h)
+        ctx.link = link
+        return z, r, rh
+
+    @staticmethod
+    def backward(ctx, dz, dr, d_rh):
+        if dz is not None or dr is not None:
+            raise DvsError("raft_update: z and r are internal to the update block; their gradients come through the blend node")
+        link = ctx.link
+        dpre, dah, dh_a = link.dpre, link.dah, link.dh_a
+        link.dpre = link.dah = link.dh_a = None
+        if dpre is None:
+            if d_rh is not None:
+                raise DvsError("raft_update: the gates node's backward ran before the blend node's of the same step (no dpre in "
+                               "the link): z must reach the blend node through this node's output")
+            return None, None, None, None, None
+        r, h = ctx.saved_tensors
+        P, hd = _rows(h)
+        # a conv_q that hands no gradient back for r * h: the z and q columns the blend node wrote still count
+        d_rh = torch.zeros_like(h) if d_rh is None else conv._nhwc(d_rh)
+        dh = _empty_map(h, hd)
+        check(_lib.lib().dvs_gru_gates_bwd(d_rh.data_ptr(), h.data_ptr(), r.data_ptr(), dh_a.data_ptr(), dpre.data_ptr(),
+                                           dah.data_ptr(), dh.data_ptr(), P, hd, _lib.stream()), "dvs_gru_gates_bwd")
+        need = ctx.needs_input_grad
+        dpre = _as_map(dpre, h, 3 * hd)
+        return (_as_map(dah, h, 2 * hd) if need[0] else None, dpre if need[1] else None, dpre if need[2] else None,
+                _as_map(dh, h, hd) if need[3] else None, None)
+
+
+class _Blend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a_q, a_x, c, z, h, link):
+        a_q, a_x, c, z, h = (conv._nhwc(t.detach()) for t in (a_q, a_x, c, z, h))
+        q, h_new = _blend_raw(a_q, a_x, c, z, h)
+        ctx.save_for_backward(z, q, h)
+        ctx.link = link
+        return h_new
+
+    @staticmethod
+    def backward(ctx, g):
+        z, q, h = ctx.saved_tensors
+        P, hd = _rows(h)
+        g = conv._nhwc(g)
+        dpre, dah, dq, dh_a = _empty_map(h, 3 * hd), _empty_map(h, 2 * hd), _empty_map(h, hd), _empty_map(h, hd)
+        check(_lib.lib().dvs_gru_blend_bwd(g.data_ptr(), z.data_ptr(), q.data_ptr(), h.data_ptr(), dpre.data_ptr(), dah.data_ptr(),
+                                           dq.data_ptr(), dh_a.data_ptr(), P, hd, _lib.stream()), "dvs_gru_blend_bwd")
+        link = ctx.link
+        link.dpre, link.dah, link.dh_a = dpre, dah, dh_a
+        # a_x, c, z and h take their gradients from the gates node (see _Link)
+        return _as_map(dq, h, hd) if ctx.needs_input_grad[0] else None, None, None, None, None, None
+
+
+def conv_gru(a_h, a_x, c, h, conv_q):
+    """h' of the split ConvGRU from the three pre-activation parts; conv_q(r * h) is the caller's convolution of the reset
+    hidden state.  Differentiable in a_h, a_x, c, h and whatever conv_q closes over."""
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in (a_h, a_x, c, h)):
+        a_h, a_x, c, h = (conv._nhwc(t) for t in (a_h, a_x, c, h))
+        z, _, rh = _gates_raw(a_h, a_x, c, h)
+        a_q = conv_q(rh)
+        if not a_q.requires_grad:
+            return _blend_raw(conv._nhwc(a_q), a_x, c, z, h)[1]
+        return _Blend.apply(a_q, a_x, c, z, h, _Link())
+    link = _Link()
+    z, _, rh = _Gates.apply(a_h, a_x, c, h, link)
+    return _Blend.apply(conv_q(rh), a_x, c, z, h, link)
+
+
+class _Weights:
+    """The kernels' view of the eighteen parameters: channels_last, the GRU's three filters stacked and cut by input block."""
+    __slots__ = ("c1", "f1", "f2", "m", "gh", "gq", "gx", "gc", "h1", "h2")
+
+
+def _drop_on_gradient(owner_ref):
+    def hook(grad):
+        owner = owner_ref()
+        if owner is not None:
+            owner._weights = owner._context = None
+    return hook
+
+
+class SmallUpdateBlock(nn.Module):
+    """update.py:99-112 with the reference's parameter names: encoder.{convc1,convf1,convf2,conv}, gru.{convz,convr,convq},
+    flow_head.{conv1,conv2}, each .weight / .bias."""
+
+    def __init__(self, hidden_dim=96, corr_levels=4, corr_radius=3):
+        super().__init__()
+        self._setup(int(hidden_dim), int(corr_levels) * (2 * int(corr_radius) + 1) ** 2, None)
+
+    @classmethod
+    def from_module(cls, block):
+        """Wrap a block of the reference's shape (duck typing: .encoder / .gru / .flow_head with the convolutions above), sharing
+        its Parameter objects."""
+        try:
+            hidden, planes = block.gru.convz.weight.shape[0], block.encoder.convc1.weight.shape[1]
+        except AttributeError as e:
+            raise DvsError("SmallUpdateBlock.from_module: not a SmallUpdateBlock (%s)" % e)
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._setup(int(hidden), int(planes), block)
+        return self
+
+    def _setup(self, hidden, planes, source):
+        if hidden <= 0 or hidden % 4:
+            raise DvsError("SmallUpdateBlock: hidden_dim=%d must be a positive multiple of 4 (16-byte channel groups)" % hidden)
+        if planes <= 0 or planes % 4:
+            raise DvsError("SmallUpdateBlock: corr_levels * (2 * corr_radius + 1)^2 = %d correlation planes must be a multiple "
+                           "of 4 (the reference's settings give 196 and 324)" % planes)
+        self.hidden_dim, self.cor_planes = hidden, planes
+        gin = hidden + CTX_DIM + MOTION_DIM
+        layout = {"encoder": [(n, co, ci if ci is not None else planes, k) for n, co, ci, k in _ENCODER],
+                  "gru": [(n, hidden, gin, 3) for n in ("convz", "convr", "convq")],
+                  "flow_head": [("conv1", 128, hidden, 3), ("conv2", 2, 128, 3)]}
+        for group, convs in layout.items():
+            holder = nn.Module()
+            for name, co, ci, k in convs:
+                if source is None:
+                    layer = nn.Conv2d(ci, co, k, padding=k // 2)        # holds the parameters (and the reference's init) only
+                else:
+                    theirs = getattr(getattr(source, group, None), name, None)
+                    w, b = getattr(theirs, "weight", None), getattr(theirs, "bias", None)
+                    if not isinstance(w, nn.Parameter) or not isinstance(b, nn.Parameter):
+                        raise DvsError("SmallUpdateBlock.from_module: %s.%s has no weight / bias parameters" % (group, name))
+                    if tuple(w.shape) != (co, ci, k, k) or tuple(b.shape) != (co,):
+                        raise DvsError("SmallUpdateBlock.from_module: %s.%s is %s / %s, expected %s / %s"
+                                       % (group, name, tuple(w.shape), tuple(b.shape), (co, ci, k, k), (co,)))
+                    layer = nn.Module()
+                    layer.weight, layer.bias = w, b
+                setattr(holder, name, layer)
+            setattr(self, group, holder)
+        self._weights = self._context = None
+
+    # ---- what is made once per context ------------------------------------------------------------------------------------
+    def _stamp(self):
+        """conv._p16_stamp's rule over every parameter (dp.FusedAdam writes weights behind torch's back), plus what decides
+        whether the derived tensors are graph nodes."""
+        gen = nn_ops.generation()
+        return (torch.is_grad_enabled(), gen) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
+
+    def _derive(self):
+        """The operands of the launches, from the parameters, by differentiable torch ops."""
+        stamp = self._stamp()
+        if self._weights is not None and self._weights[0] == stamp:
+            return self._weights[1]
+        hd = self.hidden_dim
+        e, g, f = self.encoder, self.gru, self.flow_head
+        cl = lambda t: t.contiguous(memory_format=CL)
+        pad_in = lambda t, n: F.pad(t, (0, 0, 0, 0, 0, n))                      # zero input channels behind the real ones
+        stack = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)  # [3hd, hd + 64 + 82, 3, 3]
+        w = _Weights()
+        w.c1 = (cl(e.convc1.weight), e.convc1.bias)
+        w.f1 = (cl(pad_in(e.convf1.weight, 2)), e.convf1.bias)                  # flow's 2 channels -> 4
+        w.f2 = (cl(e.convf2.weight), e.convf2.bias)
+        w.m = (cl(e.conv.weight), e.conv.bias)
+        w.gh = cl(stack[:2 * hd, :hd])
+        w.gq = cl(stack[2 * hd:, :hd])
+        w.gc = (cl(stack[:, hd:hd + CTX_DIM]), torch.cat([g.convz.bias, g.convr.bias, g.convq.bias]))
+        w.gx = cl(pad_in(stack[:, hd + CTX_DIM:], 2))                           # motion's 82 channels -> 84
+        w.h1 = (cl(f.conv1.weight), f.conv1.bias)
+        w.h2 = (cl(f.conv2.weight), f.conv2.bias)
+        self._weights, self._context = (stamp, w), None
+        if torch.is_grad_enabled():
+            # their graph is freed by the backward pass that delivers these gradients: never serve them again after it
+            hook = _drop_on_gradient(weakref.ref(self))
+            for t in (w.c1[0], w.f1[0], w.f2[0], w.m[0], w.gh, w.gq, w.gc[0], w.gc[1], w.gx, w.h1[0], w.h2[0]):
+                if t.requires_grad and not t.is_leaf:
+                    t.register_hook(hook)
+        return w
+
+    def _context_conv(self, inp, weight, bias):
+        """The hoisted convolution itself (tests count its calls)."""
+        return conv.conv2d(inp, weight, bias, padding=1)
+
+    def _hoisted(self, inp, w):
+        """c = conv(inp) + biases of the three gates, [B, 3hd, H, W]: reused while `inp` is the same tensor object with the same
+        version and requires_grad, and the weights (self._derive's stamp, which includes the grad mode) are the same."""
+        ent = self._context
+        key = (inp._version, inp.requires_grad)
+        if ent is not None and ent[0]() is inp and ent[1] == key:
+            return ent[2]
+        c = self._context_conv(inp, *w.gc)
+        if c.requires_grad:
+            c.register_hook(_drop_on_gradient(weakref.ref(self)))
+        self._context = (weakref.ref(inp), key, c)
+        return c
+
+    # ---- forward ----------------------------------------------------------------------------------------------------------
+    def _check(self, net, inp, corr, flow):
+        want = (("net", net, self.hidden_dim), ("inp", inp, CTX_DIM), ("corr", corr, self.cor_planes), ("flow", flow, 2))
+        for name, t, _ in want:
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise DvsError("SmallUpdateBlock: %s: GPU tensors only (got %s); this package has no CPU path"
+                               % (name, getattr(t, "device", type(t))))
+            if t.dtype != torch.float32:
+                raise DvsError("SmallUpdateBlock: %s: fp32 only, got %s" % (name, t.dtype))
+            if t.dim() != 4:
+                raise DvsError("SmallUpdateBlock: %s: [B,C,H,W] expected, got %s" % (name, tuple(t.shape)))
+        B, _, H, W = net.shape
+        for name, t, ch in want:
+            if tuple(t.shape) != (B, ch, H, W):
+                raise DvsError("SmallUpdateBlock: %s must be [%d,%d,%d,%d], got %s" % (name, B, ch, H, W, tuple(t.shape)))
+            if t.device != net.device:
+                raise DvsError("SmallUpdateBlock: %s on %s, net on %s" % (name, t.device, net.device))
+        for p in self.parameters():
+            if p.device != net.device or p.dtype != torch.float32:
+                raise DvsError("SmallUpdateBlock: parameters on %s / %s, inputs on %s / fp32; move the block with .to()"
+                               % (p.device, p.dtype, net.device))
+
+    def forward(self, net, inp, corr, flow):
+        self._check(net, inp, corr, flow)
+        w = self._derive()
+        c = self._hoisted(inp, w)
+        net = conv._nhwc(net)
+        # motion encoder (update.py:71-77).  flow goes in with 2 zero channels behind its own: 4 for convf1, and the same tensor
+        # closes the 80 + 2 motion channels to 84
+        flow4 = F.pad(flow.permute(0, 2, 3, 1), (0, 2)).contiguous().permute(0, 3, 1, 2)
+        cor = conv.conv2d(corr, *w.c1, act="relu")
+        flo = conv.conv2d(flow4, *w.f1, padding=3, act="relu")
+        flo = conv.conv2d(flo, *w.f2, padding=1, act="relu")
+        out = conv.conv2d(torch.cat([cor, flo], 1), *w.m, padding=1, act="relu")
+        motion = torch.cat([out, flow4], 1)
+        # ConvGRU (update.py:23-31), split by input block
+        a_x = conv.conv2d(motion, w.gx, None, padding=1)
+        a_h = conv.conv2d(net, w.gh, None, padding=1)
+        net = conv_gru(a_h, a_x, c, net, lambda rh: conv.conv2d(rh, w.gq, None, padding=1))
+        # flow head (update.py:13-14)
+        delta_flow = conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
+        return net, None, delta_flow

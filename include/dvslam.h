@@ -703,6 +703,35 @@ int dvs_altcorr_bwd(const dvs_corr_cfg* cfg, const float* fmap1, const float* fm
                     const float* coords, const float* dout, int dout_nhwc, float* dfmap1, float* dfmap2, float* dpooled, void* stream);
 int dvs_altcorr_unpool(const dvs_corr_cfg* cfg, const float* dpooled, float* dfmap2, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 11: four new entry points, nothing existing changes) ConvGRU gate arithmetic
+ *     replaces the elementwise half of ConvGRU.forward, model/raft/core/update.py:23-31 (torch.cat, torch.sigmoid, torch.tanh,
+ *     r*h, (1-z)*h + z*q); the three convolutions stay convolutions (dvs_conv2d_*), split by input-channel block.
+ *
+ *   P = B*H*W pixel rows of channels_last tensors, hd = hidden channels (hd % 4 == 0).  Row-major fp32 matrices, 16-byte aligned:
+ *       a_h [P][2hd]  conv(h), columns (z, r)             a_x [P][3hd]  conv(motion features), columns (z, r, q)
+ *       c   [P][3hd]  conv(inp) + (bz, br, bq)            a_q [P][hd]   conv(r * h)
+ *   dvs_gru_gates_fwd:  z = sigmoid((a_h[:, :hd] + a_x[:, :hd]) + c[:, :hd]),  r likewise on the next hd columns,  rh = r * h
+ *   dvs_gru_blend_fwd:  q = tanh((a_q + a_x[:, 2hd:]) + c[:, 2hd:]),  h_new = (1 - z) * h + z * q
+ *   dvs_gru_blend_bwd:  for g = dL/dh_new:  dq = g * z * (1 - q^2),  dz = g * (q - h) * z * (1 - z),  dh_a = g * (1 - z)
+ *                       writes dpre[:, :hd] = dah[:, :hd] = dz,  dpre[:, 2hd:] = dq (also as the matrix dq [P][hd]),  dh_a [P][hd]
+ *   dvs_gru_gates_bwd:  for d_rh = dL/d(r*h):  dr = d_rh * h * r * (1 - r),  dh = dh_a + d_rh * r
+ *                       writes dpre[:, hd:2hd] = dah[:, hd:] = dr,  dh [P][hd]
+ *   After both backward calls dpre [P][3hd] is the gradient of a_x and of c, dah [P][2hd] that of a_h, dq that of a_q.
+ *   expf / tanhf of the HIP math library; saturated pre-activations give exact 0, 1, -1 limits (subnormals kept), never a NaN.
+ *   Every output element is written once by one thread, no atomics: bit-reproducible.  64-bit element offsets.
+ *   DVS_ERR_INVALID for a null or misaligned pointer, hidden <= 0, hidden % 4 != 0, P == 0.
+ *   dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_gru_gates_fwd(const float* a_h, const float* a_x, const float* c, const float* h, float* z, float* r, float* rh, size_t P,
+                      int hidden, void* stream);
+int dvs_gru_blend_fwd(const float* a_q, const float* a_x, const float* c, const float* z, const float* h, float* q, float* h_new,
+                      size_t P, int hidden, void* stream);
+int dvs_gru_blend_bwd(const float* g, const float* z, const float* q, const float* h, float* dpre, float* dah, float* dq, float* dh_a,
+                      size_t P, int hidden, void* stream);
+int dvs_gru_gates_bwd(const float* d_rh, const float* h, const float* r, const float* dh_a, float* dpre, float* dah, float* dh,
+                      size_t P, int hidden, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
