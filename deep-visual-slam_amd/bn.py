@@ -236,7 +236,8 @@ def channel_stats(y, groups=1):
 
 
 def supported_c(C, bn):
-    """The fused kernels cover training-mode affine BatchNorm with C/4 dividing 256 (C = 16 ... 1024)."""
+    """The fused kernels cover training-mode affine BatchNorm with C % 4 == 0 and C/4 dividing 256: C = 4, 8, 16 ... 1024
+    (a lane owns four channels, and a workgroup's 256 lanes hold whole rows of C/4 lanes)."""
     return bn.training and bn.affine and C % 4 == 0 and (256 % (C // 4) == 0)
 
 

@@ -16,6 +16,21 @@ namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int NT = 256;
 
+// mean, clamped biased variance, inv-std and the folded scale / shift of one channel from its two sums.  The two multiply-adds are
+// spelled out: bn_fwd_fused_kernel derives these values at two places (the table the backward reads, and every workgroup's own
+// copy for z), and left to -ffp-contract the compiler fused  s1/count - mean * mean  at one of them and emitted a packed multiply
+// and a subtraction at the other.  At a large mean^2 / var the two variances then differed by the rounding of mean^2, z was written
+// with another scale / shift than the table holds, and the ReLU mask the backward recomputes from the table (y * scale + shift > 0)
+// was not the z > 0 of the forward.  One function, explicit fmaf: every site gets the same bits.
+__device__ __forceinline__ void bn_channel(float s0, float s1, float count, float eps, float g, float b, float& mean, float& var,
+                                           float& invstd, float& scale, float& shift) {
+    mean = s0 / count;
+    var = fmaxf(fmaf(-mean, mean, s1 / count), 0.f);        // biased, as used for normalisation
+    invstd = rsqrtf(var + eps);
+    scale = g * invstd;
+    shift = fmaf(-(mean * g), invstd, b);
+}
+
 // groups > 1: stats is [G][2][C], the outputs are rows of a [G][4][C] table (scale, shift, mean, invstd); the running
 // statistics receive the G momentum updates in order -- what G successive forward calls of the module would have done.
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, float count, const float* __restrict__ gamma,
@@ -51,11 +66,10 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, float count,
             s0 += st[k * slot_stride + c];
             s1 += st[k * slot_stride + C + c];
         }
-        float mean = s0 / count;
-        float var = fmaxf(s1 / count - mean * mean, 0.f);     // biased, as used for normalisation
-        float invstd = rsqrtf(var + eps);
-        scale[o] = g * invstd;
-        shift[o] = b - mean * g * invstd;
+        float mean, var, invstd, sc, sh;
+        bn_channel(s0, s1, count, eps, g, b, mean, var, invstd, sc, sh);
+        scale[o] = sc;
+        shift[o] = sh;
         mean_out[o] = mean;
         invstd_out[o] = invstd;
         float unbiased = count > 1.f ? var * count / (count - 1.f) : var;
@@ -168,11 +182,12 @@ __global__ __launch_bounds__(NT) void bn_fwd_fused_kernel(BnFusedArgs a, const f
             f32x4 sc, sh, mu, is;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                mu[j] = s0[j] / a.count;
-                const float var = fmaxf(s1[j] / a.count - mu[j] * mu[j], 0.f);
-                is[j] = rsqrtf(var + a.eps);
-                sc[j] = g[j] * is[j];
-                sh[j] = b[j] - mu[j] * g[j] * is[j];
+                float mean, var, invstd, scale, shift;        // (a vector element does not bind to a reference)
+                bn_channel(s0[j], s1[j], a.count, a.eps, g[j], b[j], mean, var, invstd, scale, shift);
+                mu[j] = mean;
+                is[j] = invstd;
+                sc[j] = scale;
+                sh[j] = shift;
                 const float unbiased = a.count > 1.f ? var * a.count / (a.count - 1.f) : var;
                 rm[j] = (1.f - a.momentum) * rm[j] + a.momentum * mu[j];
                 rv[j] = (1.f - a.momentum) * rv[j] + a.momentum * unbiased;
@@ -199,11 +214,10 @@ __global__ __launch_bounds__(NT) void bn_fwd_fused_kernel(BnFusedArgs a, const f
         const f32x4 b = a.beta ? *reinterpret_cast<const f32x4*>(a.beta + c) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float mu = s0[j] / a.count;
-            const float var = fmaxf(s1[j] / a.count - mu * mu, 0.f);
-            const float is = rsqrtf(var + a.eps);
-            s[j] = g[j] * is;
-            t[j] = b[j] - mu * g[j] * is;
+            float mean, var, invstd, scale, shift;
+            bn_channel(s0[j], s1[j], a.count, a.eps, g[j], b[j], mean, var, invstd, scale, shift);
+            s[j] = scale;                      // bit for bit the table's rows
+            t[j] = shift;
         }
         s_sc[threadIdx.x] = s;                 // thread i < C/4 holds channels 4i .. 4i+3 (c = 4i)
         s_sh[threadIdx.x] = t;

@@ -324,7 +324,7 @@ int dvs_upsample2x_bwd(const float* dy, float* dx, int B, int H, int W, int C, v
  *       bwd_apply: dy = gamma * invstd * (du - sums0/M - xhat * sums1/M); dgamma_acc / dbeta_acc (both or
  *                  neither, NULL = skip): d gamma += sums1, d beta += sums0, i.e. the parameter gradients are
  *                  accumulated in place (what autograd's AccumulateGrad would do with one more launch each).
- *     M = pixels (rows), C % 4 == 0 and C/4 divides 256 (C in {16..1024}).
+ *     M = pixels (rows), C % 4 == 0 and C/4 divides 256 (C in {4, 8, 16 .. 1024}).
  *     groups G >= 1 (PoseNet evaluates its two frame pairs as one batch, each half normalised on its own): ONE launch
  *     serves G independent sub-batches of M rows each, stored back to back -- tensors [G*M][C], stats / sums [G][2][C],
  *     scale / shift / mean / invstd = rows of a [G][4][C] table (pass the group-0 rows); gamma / beta / running
