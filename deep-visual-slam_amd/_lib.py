@@ -189,6 +189,12 @@ _SIGNATURES = {
     "dvs_gru_blend_fwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp]),
     "dvs_gru_blend_bwd": (C.c_int, [_vp] * 8 + [C.c_size_t, C.c_int, _vp]),
     "dvs_gru_gates_bwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp]),
+    "dvs_inorm_slice_pixels": (C.c_int, []),
+    "dvs_inorm_workspace": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int]),
+    "dvs_inorm_fwd": (C.c_int, [_vp] * 5 + [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_inorm_bwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_upflow8_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_upflow8_bwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,215 @@
+"""SmallRAFT's encoders on the device (model/raft/core/extractor.py:60-116, 195-267): Bottleneck stacks whose convolutions run on
+conv.conv2d and whose norm / ReLU / residual tails run on csrc/inorm.hip.
+
+    fnet = raft_encoder.SmallEncoder(128, "instance")       # raft.py:34
+    cnet = raft_encoder.SmallEncoder(160, "none")           # raft.py:35
+    fmap1, fmap2 = fnet([image1, image2])
+
+`instance_norm_act(y, norm, relu, residual)` is the tail alone:
+
+    z = (y - mean[n, c]) * invstd[n, c]  if norm     nn.InstanceNorm2d(C): no affine parameters, no running statistics, biased
+    z = max(z, 0)                        if relu     variance, eps 1e-5, the input's own statistics in train and eval mode alike
+    out = max(residual + z, 0)           if residual is not None
+
+With norm_fn='none' every relu(conv + b) is the convolution's own act="relu" and only the block's closing relu(x + relu(.)) takes
+the tail kernel (norm=False).  Parameter names and shapes are the reference's (conv1, layer{1,2,3}.{0,1}.conv{1,2,3},
+layer{2,3}.0.downsample.0, conv2; the norms have no parameters), so the fnet. / cnet. parts of raft-small.pth load with
+load_state_dict.  conv1 reads 3 channels: the image and the filter are zero-padded to 4, as raft_update pads the flow.
+GPU and fp32 only; no host synchronisation in forward or backward.
+"""
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, conv, nn_ops
+from ._lib import DvsError, check
+from .raft_update import _drop_on_gradient
+
+CL = torch.channels_last
+
+
+def slice_pixels():
+    """T: the pixels of one slice of csrc/inorm.hip (one workgroup's share of an image)."""
+    return int(_lib.lib().dvs_inorm_slice_pixels())
+
+
+def _check_map(name, t):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise DvsError("%s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
+    if t.dtype != torch.float32:
+        raise DvsError("%s: fp32 only, got %s" % (name, t.dtype))
+    if t.dim() != 4:
+        raise DvsError("%s: [N,C,H,W] expected, got %s" % (name, tuple(t.shape)))
+
+
+def _workspace(N, HW, Cn, device):
+    nbytes = int(_lib.lib().dvs_inorm_workspace(N, HW, Cn))
+    if nbytes == 0:
+        raise DvsError("instance_norm_act: unsupported shape N=%d, HW=%d, C=%d (C %% 4 == 0, HW >= 2)" % (N, HW, Cn))
+    return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
+
+
+class _InormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, residual, norm, relu):
+        y = conv._nhwc(y.detach())
+        N, Cn, H, W = y.shape
+        res = conv._nhwc(residual.detach()) if residual is not None else None
+        out = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32)
+        table = ws = None
+        nbytes = 0
+        if norm:
+            table = torch.empty((N, 2, Cn), device=y.device, dtype=torch.float32)
+            ws, nbytes = _workspace(N, H * W, Cn, y.device)
+        check(_lib.lib().dvs_inorm_fwd(y.data_ptr(), res.data_ptr() if res is not None else None, out.data_ptr(),
+                                       table.data_ptr() if norm else None, ws.data_ptr() if norm else None, nbytes, N, H * W, Cn,
+                                       int(norm), int(relu), _lib.stream()), "dvs_inorm_fwd")
+        ctx.save_for_backward(y, out if res is not None else None, table)
+        ctx.flags = (bool(norm), bool(relu))
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, out, table = ctx.saved_tensors
+        norm, relu = ctx.flags
+        N, Cn, H, W = y.shape
+        dout = conv._nhwc(dout)
+        dy = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32)
+        dres = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32) if out is not None else None
+        ws, nbytes = _workspace(N, H * W, Cn, y.device) if norm else (None, 0)
+        check(_lib.lib().dvs_inorm_bwd(dout.data_ptr(), y.data_ptr(), out.data_ptr() if out is not None else None,
+                                       table.data_ptr() if norm else None, dy.data_ptr(), dres.data_ptr() if dres is not None else None,
+                                       ws.data_ptr() if norm else None, nbytes, N, H * W, Cn, int(norm), int(relu), _lib.stream()),
+              "dvs_inorm_bwd")
+        return dy.permute(0, 3, 1, 2), dres.permute(0, 3, 1, 2) if dres is not None else None, None, None
+
+
+def instance_norm_act(y, norm=True, relu=True, residual=None):
+    """The fused tail (module docstring) of a [N,C,H,W] fp32 GPU tensor, differentiable in y and residual.  The result is in
+    channels_last memory."""
+    _check_map("instance_norm_act: y", y)
+    N, Cn, H, W = y.shape
+    if Cn % 4 or Cn < 4 or Cn > 1024:
+        raise DvsError("instance_norm_act: C=%d must be a multiple of 4 in 4 .. 1024 (16-byte channel groups)" % Cn)
+    if N < 1 or H * W < 2:
+        raise DvsError("instance_norm_act: %s: instance norm needs more than one spatial element per image (torch rejects it too)"
+                       % (tuple(y.shape),))
+    if residual is not None:
+        _check_map("instance_norm_act: residual", residual)
+        if residual.shape != y.shape or residual.device != y.device:
+            raise DvsError("instance_norm_act: residual %s on %s, y %s on %s"
+                           % (tuple(residual.shape), residual.device, tuple(y.shape), y.device))
+    return _InormAct.apply(y, residual, bool(norm), bool(relu))
+
+
+# ---- the encoder ---------------------------------------------------------------------------------------------------------------
+class _Bottleneck(nn.Module):
+    """Holds the parameters of one BottleneckBlock (extractor.py:60-104) under the reference's names."""
+
+    def __init__(self, in_planes, planes, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_planes, planes // 4, kernel_size=1, padding=0)
+        self.conv2 = nn.Conv2d(planes // 4, planes // 4, kernel_size=3, padding=1, stride=stride)
+        self.conv3 = nn.Conv2d(planes // 4, planes, kernel_size=1, padding=0)
+        self.stride = stride
+        self.downsample = None if stride == 1 else nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride))
+
+
+class SmallEncoder(nn.Module):
+    def __init__(self, output_dim=128, norm_fn="instance", dropout=0.0):
+        super().__init__()
+        if norm_fn not in ("instance", "none"):
+            raise DvsError("SmallEncoder: norm_fn=%r is not built: SmallRAFT uses 'instance' (fnet) and 'none' (cnet) only" % (norm_fn,))
+        if dropout and dropout > 0:
+            raise DvsError("SmallEncoder: dropout=%r is not built: SmallRAFT forces it to 0 (raft.py:29)" % (dropout,))
+        if int(output_dim) <= 0 or int(output_dim) % 4:
+            raise DvsError("SmallEncoder: output_dim=%r must be a positive multiple of 4" % (output_dim,))
+        self.norm_fn = norm_fn
+        self.conv1 = nn.Conv2d(3, 32, kernel_size=7, stride=2, padding=3)
+        planes = 32
+        for i, (dim, stride) in enumerate(((32, 1), (64, 2), (96, 2)), 1):
+            setattr(self, "layer%d" % i, nn.Sequential(_Bottleneck(planes, dim, stride), _Bottleneck(dim, dim, 1)))
+            planes = dim
+        self.conv2 = nn.Conv2d(96, int(output_dim), kernel_size=1)
+        for m in self.modules():                                        # extractor.py:226-228
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        self._weights = self._context = None
+
+    def _blocks(self):
+        return [b for i in (1, 2, 3) for b in getattr(self, "layer%d" % i)]
+
+    def _convs(self):
+        out = [self.conv1]
+        for b in self._blocks():
+            out += [b.conv1, b.conv2, b.conv3] + ([b.downsample[0]] if b.downsample is not None else [])
+        return out + [self.conv2]
+
+    def _derive(self):
+        """{conv module: (channels_last weight, bias)}, conv1's filter zero-padded to 4 input channels: made by differentiable
+        torch ops and kept under raft_update's stamp rule (parameter versions and nn_ops.generation(), which dp.FusedAdam bumps)."""
+        stamp = (torch.is_grad_enabled(), nn_ops.generation()) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
+        if self._weights is not None and self._weights[0] == stamp:
+            return self._weights[1]
+        w = {}
+        for m in self._convs():
+            wt = F.pad(m.weight, (0, 0, 0, 0, 0, 1)) if m is self.conv1 else m.weight
+            w[m] = (wt.contiguous(memory_format=CL), m.bias)
+        self._weights = (stamp, w)
+        if torch.is_grad_enabled():
+            hook = _drop_on_gradient(weakref.ref(self))     # their graph is freed by the backward pass that delivers these gradients
+            for wt, _ in w.values():
+                if wt.requires_grad and not wt.is_leaf:
+                    wt.register_hook(hook)
+        return w
+
+    def _block(self, b, w, x):
+        norm = self.norm_fn == "instance"
+        s = b.stride
+        if norm:
+            y = instance_norm_act(conv.conv2d(x, *w[b.conv1]))
+            y = instance_norm_act(conv.conv2d(y, *w[b.conv2], stride=s, padding=1))
+        else:
+            y = conv.conv2d(x, *w[b.conv1], act="relu")
+            y = conv.conv2d(y, *w[b.conv2], stride=s, padding=1, act="relu")
+        y = conv.conv2d(y, *w[b.conv3])
+        if b.downsample is not None:
+            x = conv.conv2d(x, *w[b.downsample[0]], stride=s)
+            if norm:
+                x = instance_norm_act(x, relu=False)
+        return instance_norm_act(y, norm=norm, relu=True, residual=x)          # relu(x + relu(norm3(conv3(.)))), extractor.py:111-116
+
+    def forward(self, x):
+        is_list = isinstance(x, (tuple, list))
+        if is_list:
+            if len(x) != 2:
+                raise DvsError("SmallEncoder: a list input holds two image batches (extractor.py:246-265), got %d" % len(x))
+            for t in x:
+                _check_map("SmallEncoder: input", t)
+            if x[0].shape != x[1].shape:
+                raise DvsError("SmallEncoder: the two batches differ: %s and %s" % (tuple(x[0].shape), tuple(x[1].shape)))
+            batch_dim = x[0].shape[0]
+            x = torch.cat(list(x), 0)
+        _check_map("SmallEncoder: input", x)
+        if x.shape[1] != 3:
+            raise DvsError("SmallEncoder: 3 input channels expected, got %s" % (tuple(x.shape),))
+        if x.shape[2] < 16 or x.shape[3] < 16:
+            raise DvsError("SmallEncoder: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (tuple(x.shape),))
+        for p in self.parameters():
+            if p.device != x.device or p.dtype != torch.float32:
+                raise DvsError("SmallEncoder: parameters on %s / %s, input on %s / fp32; move the module with .to()"
+                               % (p.device, p.dtype, x.device))
+        w = self._derive()
+        x4 = F.pad(x.permute(0, 2, 3, 1), (0, 1)).permute(0, 3, 1, 2)           # NHWC memory, a zero fourth channel
+        if self.norm_fn == "instance":
+            x = instance_norm_act(conv.conv2d(x4, *w[self.conv1], stride=2, padding=3))
+        else:
+            x = conv.conv2d(x4, *w[self.conv1], stride=2, padding=3, act="relu")
+        for b in self._blocks():
+            x = self._block(b, w, x)
+        x = conv.conv2d(x, *w[self.conv2])
+        if is_list:
+            return torch.split(x, [batch_dim, batch_dim], dim=0)
+        return x

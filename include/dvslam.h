@@ -732,6 +732,49 @@ int dvs_gru_blend_bwd(const float* g, const float* z, const float* q, const floa
 int dvs_gru_gates_bwd(const float* d_rh, const float* h, const float* r, const float* dh_a, float* dpre, float* dah, float* dh,
                       size_t P, int hidden, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 11: new entry points only) Instance norm with the Bottleneck tail fused
+ *     replaces nn.InstanceNorm2d + ReLU + the residual add + ReLU of BottleneckBlock.forward, model/raft/core/extractor.py:107-116,
+ *     and, with norm = 0, the same tail of the 'none' encoder.
+ *
+ *   fp32 NHWC activations [N][HW][C], C % 4 == 0 (4 .. 1024), HW >= 2, N <= 65535, 16-byte aligned.
+ *       z   = norm ? (y - mean[n][c]) * invstd[n][c] : y        mean, biased variance over the HW pixels of image n, eps = 1e-5,
+ *       z   = relu ? max(z, 0) : z                              no affine parameters, no running statistics
+ *       out = residual ? max(residual + z, 0) : z               residual == NULL: none
+ *   table [N][2][C] (mean, invstd), written by the forward with norm = 1 and read by the backward; NULL allowed with norm = 0.
+ *   dvs_inorm_bwd: for dout = dL/dout, with `out` the forward's output (and dresidual) exactly when there was a residual:
+ *       g  = residual ? dout * [out > 0] : dout                 written to dresidual
+ *       du = relu ? g * [z > 0] : g                             z recomputed from y and the table by the forward's own expression
+ *       dy = norm ? invstd * (du - mean_hw(du) - xhat * mean_hw(du * xhat)) : du
+ *   Statistics: per slice of dvs_inorm_slice_pixels() = 1024 pixels the mean first, then the squared deviations around it; the
+ *       slices' (count, mean, M2) are merged with Chan's formula.  No sum of squares minus squared mean, no atomics, a fixed
+ *       order: bit-reproducible, and an image's result does not depend on the other images of the batch.
+ *   workspace: dvs_inorm_workspace(N, HW, C) bytes (0 for invalid arguments), device memory, 16-byte aligned, needed with norm = 1;
+ *       the backward may reuse the forward's.
+ *   DVS_ERR_INVALID, before any launch, for a null or misaligned pointer, C % 4 != 0, HW < 2, N or HW out of range, a workspace
+ *       that is too small.  dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_inorm_slice_pixels(void);
+size_t dvs_inorm_workspace(int N, size_t HW, int C);
+int dvs_inorm_fwd(const float* y, const float* residual, float* out, float* table, void* workspace, size_t workspace_bytes, int N,
+                  size_t HW, int C, int norm, int relu, void* stream);
+int dvs_inorm_bwd(const float* dout, const float* y, const float* out, const float* table, float* dy, float* dresidual,
+                  void* workspace, size_t workspace_bytes, int N, size_t HW, int C, int norm, int relu, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 11: new entry points only) upflow8
+ *     replaces upflow8, model/raft/core/utils/utils.py:80-82: 8 * F.interpolate(flow, 8x, mode='bilinear', align_corners=True)
+ *
+ *   flow [N][2][h][w] (flow_nchw = 1) or [N][h][w][2] (flow_nchw = 0, channels_last memory); out [N][2][8h][8w] planar.
+ *   torch's index arithmetic in fp32: scale = (in - 1) / (out - 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1),
+ *   l1 = src - i0, l0 = 1 - l1; the factor 8 is applied to the finished blend.
+ *   dvs_upflow8_bwd: dflow (layout by dflow_nchw, overwritten) = the adjoint applied to dout [N][2][8h][8w]: a gather with the
+ *   forward's weights, fixed order, no atomics.  Both directions are bit-reproducible.
+ *   N <= 65535, h, w >= 1, 64 * h * w < 2^31; 16-byte aligned pointers.  DVS_ERR_INVALID before any launch otherwise.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_upflow8_fwd(const float* flow, float* out, int N, int h, int w, int flow_nchw, void* stream);
+int dvs_upflow8_bwd(const float* dout, float* dflow, int N, int h, int w, int dflow_nchw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
