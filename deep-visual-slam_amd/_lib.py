@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first; see module docstri
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVS_LIB") or os.path.join(HERE, "libdvslam_hip.so")    # DVS_LIB: A/B builds (tools/build_variant.py)
 MAX_SCALES = 4
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _vp = C.c_void_p
 
@@ -73,17 +73,13 @@ _SIGNATURES = {
     "dvs_conv2d_fwd": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ConvDesc), C.POINTER(ConvFusion), _vp]),
     "dvs_wino_weights": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_conv3x3_wino_gen": (C.c_int, [_vp, _vp, _vp, _vp, _vp] + [C.c_int] * 13 + [_vp]),
-    "dvs_conv3x3_wino_wgrad": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "dvs_conv3x3_wino_wgrad_gen": (C.c_int, [_vp] * 6 + [C.c_int] * 9 + [_vp]),
     "dvs_conv3x3_wino_wgrad_workspace": (C.c_size_t, [C.c_int] * 6),
-    "dvs_conv3x3_wino_wgrad_ws": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
-    "dvs_conv3x3_wino_wgrad_gen_ws": (C.c_int, [_vp] * 6 + [C.c_int] * 9 + [_vp, C.c_size_t, _vp]),
+    "dvs_conv3x3_wino_wgrad": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "dvs_conv3x3_wino_wgrad_gen": (C.c_int, [_vp] * 6 + [C.c_int] * 9 + [_vp, C.c_size_t, _vp]),
     "dvs_peak_probe_mfma": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), _vp]),
     "dvs_peak_probe_copy": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "dvs_wino_weights_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
-    "dvs_conv3x3_wino_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      _vp]),
-    "dvs_conv3x3_wino_fwd_slots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 9 + [_vp]),
+    "dvs_conv3x3_wino_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 9 + [_vp]),
     "dvs_conv3x3_bf16_pack": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_conv3x3_bf16_wgrad": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 6 + [_vp]),
     "dvs_conv3x3_bf16_wgrad_gen": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 10 + [_vp]),
@@ -93,36 +89,27 @@ _SIGNATURES = {
     "dvs_conv2d_pack_wt_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "dvs_reflect_fold": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_act_bwd": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, _vp]),
-    "dvs_conv2d_dgrad": (C.c_int, [_vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_int, _vp, C.c_int, _vp]),
-    "dvs_conv2d_dgrad_res": (C.c_int, [_vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
-    "dvs_conv2d_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ConvDesc), C.POINTER(ConvFusion), _vp, C.c_int, _vp]),
+    "dvs_conv2d_dgrad": (C.c_int, [_vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     "dvs_conv2d_wgrad_workspace": (C.c_size_t, [C.POINTER(ConvDesc), C.POINTER(ConvFusion), C.c_int, C.c_int]),
-    "dvs_conv2d_wgrad_ws": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ConvDesc), C.POINTER(ConvFusion), _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "dvs_conv2d_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ConvDesc), C.POINTER(ConvFusion), _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "dvs_conv2d_head_fwd": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ConvDesc), C.c_int, _vp]),
-    "dvs_conv2d_head_bwd": (C.c_int, [_vp] * 7 + [C.POINTER(ConvDesc), C.c_int, _vp]),
-    "dvs_conv2d_head_bwd_res": (C.c_int, [_vp] * 7 + [C.POINTER(ConvDesc), C.c_int, _vp, _vp]),
+    "dvs_conv2d_head_bwd": (C.c_int, [_vp] * 7 + [C.POINTER(ConvDesc), C.c_int, _vp, _vp]),
     "dvs_maxpool3x3s2_fwd": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "dvs_maxpool3x3s2_bwd": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "dvs_maxpool3x3s2_bwd_res": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_maxpool3x3s2_bwd": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_upsample2x_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_upsample2x_bwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_bn_bwd_slot_floats": (C.c_int, [C.c_int, C.c_int]),
     "dvs_bn_bwd": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int, _vp]),
     "dvs_bn_relu_maxpool_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_bn_relu_maxpool_bwd": (C.c_int, [_vp] * 9 + [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
-    "dvs_bn_finalize": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
-    "dvs_bn_fwd": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
+    "dvs_bn_finalize": (C.c_int, [_vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                  C.c_int, _vp]),
+    "dvs_bn_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
                               C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
-    "dvs_bn_finalize_slots": (C.c_int, [_vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp,
-                                        C.c_int, _vp]),
-    "dvs_bn_fwd_slots": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_bn_apply_fwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_bn_bwd_workspace": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
-    "dvs_bn_bwd_reduce": (C.c_int, [_vp] * 8 + [C.c_size_t, C.c_int, C.c_int, _vp]),
-    "dvs_bn_bwd_apply": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, _vp, _vp, C.c_int, _vp]),
-    "dvs_bn_bwd_reduce_ymask": (C.c_int, [_vp] * 8 + [C.c_size_t, C.c_int, C.c_int, _vp]),
-    "dvs_bn_bwd_apply_ymask": (C.c_int, [_vp] * 9 + [C.c_size_t, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "dvs_bn_bwd_reduce": (C.c_int, [_vp] * 4 + [C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
+    "dvs_bn_bwd_apply": (C.c_int, [_vp] * 3 + [C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int, _vp]),
     "dvs_last_error": (C.c_char_p, []),
     "dvs_set_deterministic": (C.c_int, [C.c_int]),
     "dvs_get_deterministic": (C.c_int, []),

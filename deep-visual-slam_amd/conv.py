@@ -485,9 +485,9 @@ def conv3x3_wino(x, weight, stats=None, stat_groups=0, flip=False, residual=None
     convolution, x = dY [B,Cout,H,W] -> dX [B,Cin,H,W].  `weight` must be the parameter object itself (the operand cache is pinned to it)."""
     x, u, y, residual, (B, k, H, W), n = _plain_operands("conv3x3_wino", x, weight, flip, residual, _wino_weight)
     # stat_slots > 1: stats is [stat_slots][G][2][N]; the BatchNorm kernels add the copies up (bn.bn_act)
-    check(_lib.lib().dvs_conv3x3_wino_fwd_slots(x.data_ptr(), u.data_ptr(), ptr(bias), residual.data_ptr() if residual is not None else None,
-                                                y.data_ptr(), ptr(stats), stat_groups if stats is not None else 0, int(stat_slots),
-                                                B, H, W, k, n, int(bool(relu)), int(flip), _lib.stream()), "dvs_conv3x3_wino_fwd")
+    check(_lib.lib().dvs_conv3x3_wino_fwd(x.data_ptr(), u.data_ptr(), ptr(bias), residual.data_ptr() if residual is not None else None,
+                                          y.data_ptr(), ptr(stats), stat_groups if stats is not None else 0, int(stat_slots),
+                                          B, H, W, k, n, int(bool(relu)), int(flip), _lib.stream()), "dvs_conv3x3_wino_fwd")
     return y
 
 
@@ -539,8 +539,8 @@ def conv3x3_wino_wgrad(x, dy, weight_shape, dw_out=None, pooled=False):
     B, _, H, W = x.shape
     dw = _sink_or_zeros("conv3x3_wino_wgrad", dw_out, weight_shape, dy.device, pooled)
     ws, nws = _wgrad_workspace(B, H, W, ci, co, dy.device)
-    check(_lib.lib().dvs_conv3x3_wino_wgrad_ws(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ci, co, _WINO_WGS,
-                                               ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad")
+    check(_lib.lib().dvs_conv3x3_wino_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ci, co, _WINO_WGS,
+                                            ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad")
     return None if dw_out is not None else dw
 
 
@@ -585,9 +585,9 @@ def conv3x3_wino_wgrad_gen(x, x2, dy, weight_shape, dw_out=None, pooled=False, y
     x, skip, up, B, c1, c2, H, W, dy, yo, dact, dw, db = _wgrad_gen_operands(
         "conv3x3_wino_wgrad_gen", x, x2, dy, weight_shape, dw_out, pooled, y_out, act, want_bias, db_out)
     ws, nws = _wgrad_workspace(B, H, W, max(c1, c2), weight_shape[0], dy.device)
-    check(_lib.lib().dvs_conv3x3_wino_wgrad_gen_ws(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(), yo,
-                                                   dw.data_ptr(), ptr(db), B, H, W, c1, c2, weight_shape[0], int(up), dact, _WINO_WGS,
-                                                   ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad_gen")
+    check(_lib.lib().dvs_conv3x3_wino_wgrad_gen(x.data_ptr(), skip.data_ptr() if skip is not None else None, dy.data_ptr(), yo,
+                                                dw.data_ptr(), ptr(db), B, H, W, c1, c2, weight_shape[0], int(up), dact, _WINO_WGS,
+                                                ptr(ws), nws, _lib.stream()), "dvs_conv3x3_wino_wgrad_gen")
     return (None if dw_out is not None else dw), (None if db_out is not None else db)
 
 
@@ -607,21 +607,20 @@ def conv2d_dgrad(dy, weight, x_shape, stride, pad, reflect, y_out=None, act=None
         d.pad_mode = 2           # x_shape is the reflection-padded input: zero padding, unpadded flops in the profile
     dact = ACT[act]
     yo = _nhwc(y_out).data_ptr() if dact else None
+    dskip = None
     if split_c1:
         if residual is not None:
             raise _lib.DvsError("conv2d_dgrad: a residual cannot be combined with the upsample+concat split")
         dx = zeropool.zeros((B, H // 2, W // 2, split_c1), dy.device).permute(0, 3, 1, 2)      # NHWC memory
-        dskip = (torch.empty((B, Cin - split_c1, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
-                 if split_c1 < Cin else None)
-        check(l.dvs_conv2d_dgrad(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), yo, dact,
-                                 dskip.data_ptr() if dskip is not None else None, split_c1, _lib.stream()),
-              "dvs_conv2d_dgrad")
-        return dx, dskip
-    dx = torch.empty((B, Cin, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
-    residual = _checked_residual("conv2d_dgrad", residual, dx, "gradient")
-    check(l.dvs_conv2d_dgrad_res(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), yo, dact, None, 0,
-                                 residual.data_ptr() if residual is not None else None, _lib.stream()), "dvs_conv2d_dgrad")
-    return dx
+        if split_c1 < Cin:
+            dskip = torch.empty((B, Cin - split_c1, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
+    else:
+        dx = torch.empty((B, Cin, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
+        residual = _checked_residual("conv2d_dgrad", residual, dx, "gradient")
+    check(l.dvs_conv2d_dgrad(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), yo, dact,
+                             dskip.data_ptr() if dskip is not None else None, split_c1,
+                             residual.data_ptr() if residual is not None else None, _lib.stream()), "dvs_conv2d_dgrad")
+    return (dx, dskip) if split_c1 else dx
 
 
 def conv2d_wgrad(x, dy, weight_shape, stride, pad, reflect, want_bias, y_out=None, act=None, x2=None, in_scale=None,
@@ -642,8 +641,8 @@ def conv2d_wgrad(x, dy, weight_shape, stride, pad, reflect, want_bias, y_out=Non
     if _WGRAD_ORDERED or _lib.deterministic():               # slab workspace: partial tiles + an ordered second pass, no atomics on dw
         nws = l.dvs_conv2d_wgrad_workspace(C.byref(d), C.byref(f), dact, int(db is not None))
         ws = torch.empty(nws // 4, device=dy.device, dtype=torch.float32) if nws else None
-    check(l.dvs_conv2d_wgrad_ws(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ptr(db), C.byref(d), C.byref(f), yo, dact,
-                                ptr(ws), nws, _lib.stream()), "dvs_conv2d_wgrad")
+    check(l.dvs_conv2d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ptr(db), C.byref(d), C.byref(f), yo, dact,
+                             ptr(ws), nws, _lib.stream()), "dvs_conv2d_wgrad")
     if nchw_planar:
         dw = dw[..., :kw]
     return (None if dw_out is not None else dw), (None if db_out is not None else db)
@@ -927,9 +926,9 @@ class _HeadConv(torch.autograd.Function):
         res = None
         if dxa is not None and dx is not None:
             res = _nhwc(dxa)
-        check(_lib.lib().dvs_conv2d_head_bwd_res(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(),
-                                                 dx.data_ptr() if dx is not None else None, dw.data_ptr(), ptr(db), C.byref(d),
-                                                 ACT[act], res.data_ptr() if res is not None else None, _lib.stream()),
+        check(_lib.lib().dvs_conv2d_head_bwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(),
+                                             dx.data_ptr() if dx is not None else None, dw.data_ptr(), ptr(db), C.byref(d),
+                                             ACT[act], res.data_ptr() if res is not None else None, _lib.stream()),
               "dvs_conv2d_head_bwd")
         if wsink is not None:
             dw = None

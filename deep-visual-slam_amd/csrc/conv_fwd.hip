@@ -809,12 +809,7 @@ int dvs_conv2d_pack_wt(const float* w, float* wt, int Cout, int Cin, int kh, int
 }
 
 int dvs_conv2d_dgrad(const float* dy, const float* wt, float* dx, const dvs_conv_desc* d, const float* y_out,
-                     int dact, float* dx_skip, int C1, void* stream) {
-    return dvs_conv2d_dgrad_res(dy, wt, dx, d, y_out, dact, dx_skip, C1, nullptr, stream);
-}
-
-int dvs_conv2d_dgrad_res(const float* dy, const float* wt, float* dx, const dvs_conv_desc* d, const float* y_out,
-                         int dact, float* dx_skip, int C1, const float* residual, void* stream) {
+                     int dact, float* dx_skip, int C1, const float* residual, void* stream) {
     DVS_REQUIRE(dy && wt && dx && d, "dvs_conv2d_dgrad: null pointer");
     DVS_REQUIRE(!residual || (C1 == 0 && residual != dx), "dvs_conv2d_dgrad: a residual excludes the upsample+concat split and may not alias dx");
     DVS_REQUIRE(C1 == 0 || (d->stride == 1 && (d->H & 1) == 0 && (d->W & 1) == 0 && C1 <= d->Cin &&

@@ -26,7 +26,7 @@ struct HeadParams {
     float* y;            // [B,H,W,Cout]   (stride 1, "same" size)
     const float* dy;     // backward: gradient of y (post-activation)
     float* dx;           // [B,H,W,Cin]
-    const float* dx_res; // optional [B,H,W,Cin]: another gradient of x, added to dx (dvs_conv2d_head_bwd_res)
+    const float* dx_res; // optional [B,H,W,Cin]: another gradient of x, added to dx (dvs_conv2d_head_bwd)
     float* dw;           // [Cout][Ktot], atomics
     float* dbias;        // [Cout], atomics
     int B, H, W, Cin, Cout, k, pad, reflect, act;
@@ -829,12 +829,7 @@ int dvs_conv2d_head_fwd(const float* x, const float* w, const float* bias, float
 }
 
 int dvs_conv2d_head_bwd(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
-                        float* dbias, const dvs_conv_desc* d, int act, void* stream) {
-    return dvs_conv2d_head_bwd_res(x, w, y, dy, dx, dw, dbias, d, act, nullptr, stream);
-}
-
-int dvs_conv2d_head_bwd_res(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
-                            float* dbias, const dvs_conv_desc* d, int act, const float* dx_residual, void* stream) {
+                        float* dbias, const dvs_conv_desc* d, int act, const float* dx_residual, void* stream) {
     DVS_REQUIRE(x && w && y && dy && dw, "dvs_conv2d_head_bwd: null pointer");
     DVS_REQUIRE(!dx_residual || (dx && dx_residual != dx), "dvs_conv2d_head_bwd: the residual needs dx and may not alias it");
     HeadParams p{};

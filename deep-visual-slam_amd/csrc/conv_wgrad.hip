@@ -790,11 +790,6 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
     return need ? DVS_OK : dvs::check_launch("dvs_conv2d_wgrad");
 }
 
-int dvs_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d,
-                     const dvs_conv_fusion* f, const float* y_out, int dact, void* stream) {
-    return wgrad_impl(x, dy, dw, dbias, d, f, y_out, dact, nullptr, 0, nullptr, stream);
-}
-
 size_t dvs_conv2d_wgrad_workspace(const dvs_conv_desc* d, const dvs_conv_fusion* f, int dact, int with_bias) {
     size_t need = 0;
     static float dummy;
@@ -803,11 +798,11 @@ size_t dvs_conv2d_wgrad_workspace(const dvs_conv_desc* d, const dvs_conv_fusion*
     return need;
 }
 
-int dvs_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d, const dvs_conv_fusion* f,
-                        const float* y_out, int dact, float* workspace, size_t workspace_bytes, void* stream) {
+int dvs_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d, const dvs_conv_fusion* f,
+                     const float* y_out, int dact, float* workspace, size_t workspace_bytes, void* stream) {
     if (workspace) {
         const size_t need = dvs_conv2d_wgrad_workspace(d, f, dact, dbias != nullptr);
-        DVS_REQUIRE(workspace_bytes >= need, "dvs_conv2d_wgrad_ws: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        DVS_REQUIRE(workspace_bytes >= need, "dvs_conv2d_wgrad: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     }
     return wgrad_impl(x, dy, dw, dbias, d, f, y_out, dact, workspace, workspace_bytes, nullptr, stream);
 }

@@ -560,7 +560,7 @@ __global__ __launch_bounds__(NT, 1) void wino_fwd_kernel(WinoParams p) {
     if (want_stats) {
         // One workgroup per CU: a workgroup's last act is these atomics, and its CU stays occupied until they are acknowledged.  Thousands
         // of workgroups adding to the SAME 2 x Cout addresses serialise in the L2 (~35 ns each: +120 us on a 140 us layer-1 launch at
-        // batch 24), so the workgroups spread over several copies of the table that the BatchNorm kernel adds up (dvs_bn_fwd_slots).
+        // batch 24), so the workgroups spread over several copies of the table that the BatchNorm kernel adds up (dvs_bn_fwd).
         float* st = p.stats + (size_t)((int)blockIdx.x & p.stat_mask) * p.stat_stride;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -1152,13 +1152,7 @@ int dvs_wino_weights_batch(const void* table, int n_entries, int total_workgroup
 }
 
 int dvs_conv3x3_wino_fwd(const float* x, const float* u, const float* bias, const float* res, float* y, float* stats, int stat_groups,
-                         int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad, void* stream) {
-    return dvs_conv3x3_wino_fwd_slots(x, u, bias, res, y, stats, stat_groups, 1, B, H, W, Cin, Cout, relu, as_dgrad, stream);
-}
-
-int dvs_conv3x3_wino_fwd_slots(const float* x, const float* u, const float* bias, const float* res, float* y, float* stats,
-                               int stat_groups, int stat_slots, int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad,
-                               void* stream) {
+                         int stat_slots, int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad, void* stream) {
     DVS_REQUIRE(x && u && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "dvs_conv3x3_wino_fwd: bad argument");
     DVS_REQUIRE(stat_slots >= 1 && stat_slots <= 64 && (stat_slots & (stat_slots - 1)) == 0,
                 "dvs_conv3x3_wino_fwd: stat_slots must be a power of two in [1, 64] (got %d)", stat_slots);
@@ -1211,15 +1205,15 @@ size_t dvs_conv3x3_wino_wgrad_workspace(int B, int H, int W, int Cin, int Cout, 
     return (size_t)(Cin / 32) * (Cout / 32) * sp.S * 9 * 1024 * sizeof(float);
 }
 
-int dvs_conv3x3_wino_wgrad_ws(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int target_workgroups,
-                              float* workspace, size_t workspace_bytes, void* stream) {
+int dvs_conv3x3_wino_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int target_workgroups,
+                           float* workspace, size_t workspace_bytes, void* stream) {
     DVS_REQUIRE(x && dy && dw && B > 0 && H > 0 && W > 0, "dvs_conv3x3_wino_wgrad: bad argument");
     DVS_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0 && Cin > 0 && Cout > 0, "dvs_conv3x3_wino_wgrad: channel counts must be multiples of 32 (got %d, %d)",
                 Cin, Cout);
     DVS_REQUIRE(((double)B * H * W + W + 1) * (Cin > Cout ? Cin : Cout) * 4 + 8192 < 1073741824.0,
                 "dvs_conv3x3_wino_wgrad: tensors must be smaller than 1 GiB (32-bit buffer offsets with two mask bits)");
     DVS_REQUIRE(!workspace || workspace_bytes >= dvs_conv3x3_wino_wgrad_workspace(B, H, W, Cin, Cout, target_workgroups),
-                "dvs_conv3x3_wino_wgrad_ws: workspace of %zu bytes is too small", workspace_bytes);
+                "dvs_conv3x3_wino_wgrad: workspace of %zu bytes is too small", workspace_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     dvs::ProfScope prof(dvs::SLOT_CONV_WGRAD, st);       // flops of the direct weight gradient
     prof.work(2.0 * B * H * W * Cout * (double)Cin * 9);
@@ -1227,14 +1221,9 @@ int dvs_conv3x3_wino_wgrad_ws(const float* x, const float* dy, float* dw, int B,
     return dvs::check_launch("dvs_conv3x3_wino_wgrad");
 }
 
-int dvs_conv3x3_wino_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int target_workgroups,
-                           void* stream) {
-    return dvs_conv3x3_wino_wgrad_ws(x, dy, dw, B, H, W, Cin, Cout, target_workgroups, nullptr, 0, stream);
-}
-
-int dvs_conv3x3_wino_wgrad_gen_ws(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H,
-                                  int W, int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, float* workspace,
-                                  size_t workspace_bytes, void* stream) {
+int dvs_conv3x3_wino_wgrad_gen(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H,
+                               int W, int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, float* workspace,
+                               size_t workspace_bytes, void* stream) {
     DVS_REQUIRE(x && dy && dw && B > 0 && H >= 2 && W >= 2, "dvs_conv3x3_wino_wgrad_gen: bad argument (ReflectionPad2d(1) needs H, W >= 2)");
     DVS_REQUIRE((C2 == 0) == (x2 == nullptr) && C2 >= 0, "dvs_conv3x3_wino_wgrad_gen: x2 and C2 go together");
     DVS_REQUIRE(C1 > 0 && C1 % 32 == 0 && C2 % 32 == 0 && Cout > 0 && Cout % 32 == 0,
@@ -1248,7 +1237,7 @@ int dvs_conv3x3_wino_wgrad_gen_ws(const float* x, const float* x2, const float* 
     DVS_REQUIRE(((double)B * H * W + 3 * W + 3) * cmax * 4 + 8192 < 1073741824.0,
                 "dvs_conv3x3_wino_wgrad_gen: tensors must be smaller than 1 GiB (32-bit buffer offsets with two mask bits)");
     DVS_REQUIRE(!workspace || workspace_bytes >= dvs_conv3x3_wino_wgrad_workspace(B, H, W, C1 > C2 ? C1 : C2, Cout, target_workgroups),
-                "dvs_conv3x3_wino_wgrad_gen_ws: workspace of %zu bytes is too small", workspace_bytes);
+                "dvs_conv3x3_wino_wgrad_gen: workspace of %zu bytes is too small", workspace_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     dvs::ProfScope prof(dvs::SLOT_CONV_WGRAD, st);       // flops of the direct weight gradient
     prof.work(2.0 * B * H * W * Cout * (double)(C1 + C2) * 9);
@@ -1264,12 +1253,6 @@ int dvs_conv3x3_wino_wgrad_gen_ws(const float* x, const float* x2, const float* 
         if (C2) launch_wino_wgrad<1>(x2, dy, dw + C1, B, H, W, C2, Cout, Ct, tw, st, nullptr, 0, nullptr, ws);
     }
     return dvs::check_launch("dvs_conv3x3_wino_wgrad_gen");
-}
-
-int dvs_conv3x3_wino_wgrad_gen(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H, int W,
-                               int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, void* stream) {
-    return dvs_conv3x3_wino_wgrad_gen_ws(x, x2, dy, y_out, dw, dbias, B, H, W, C1, C2, Cout, upsample, dact, target_workgroups, nullptr, 0,
-                                         stream);
 }
 
 }  // extern "C"

@@ -178,7 +178,7 @@ int dvs_set_precision(int mode) {
 
 int dvs_get_precision(void) { return dvs::g_precision.load(); }
 
-int dvs_abi_version(void) { return 11; }
+int dvs_abi_version(void) { return 12; }
 
 const char* dvs_arch(void) { return "gfx950"; }
 

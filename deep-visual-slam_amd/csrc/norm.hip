@@ -668,16 +668,9 @@ inline unsigned stream_grid(size_t n4) {
 
 extern "C" {
 
-int dvs_bn_finalize(const float* stats, double count, const float* gamma, const float* beta, float* running_mean,
+int dvs_bn_finalize(const float* stats, int stat_slots, double count, const float* gamma, const float* beta, float* running_mean,
                     float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
                     float* invstd, int C, long long* num_batches_tracked, int groups, void* stream) {
-    return dvs_bn_finalize_slots(stats, 1, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean, invstd, C,
-                                 num_batches_tracked, groups, stream);
-}
-
-int dvs_bn_finalize_slots(const float* stats, int stat_slots, double count, const float* gamma, const float* beta, float* running_mean,
-                          float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
-                          float* invstd, int C, long long* num_batches_tracked, int groups, void* stream) {
     DVS_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count >= 1 && groups >= 1 && stat_slots >= 1,
                 "dvs_bn_finalize: bad argument");
     DVS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "dvs_bn_finalize: running stats come together");
@@ -687,18 +680,10 @@ int dvs_bn_finalize_slots(const float* stats, int stat_slots, double count, cons
     return dvs::check_launch("dvs_bn_finalize");
 }
 
-int dvs_bn_fwd(const float* y, const float* stats, double count, const float* gamma, const float* beta,
+int dvs_bn_fwd(const float* y, const float* stats, int stat_slots, double count, const float* gamma, const float* beta,
                float* running_mean, float* running_var, float momentum, float eps, long long* num_batches_tracked,
                float* fin, const float* residual, const float* res_scale, const float* res_shift, float* z, size_t M,
                int C, int relu, int groups, void* stream) {
-    return dvs_bn_fwd_slots(y, stats, 1, count, gamma, beta, running_mean, running_var, momentum, eps, num_batches_tracked, fin,
-                            residual, res_scale, res_shift, z, M, C, relu, groups, stream);
-}
-
-int dvs_bn_fwd_slots(const float* y, const float* stats, int stat_slots, double count, const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, long long* num_batches_tracked,
-                     float* fin, const float* residual, const float* res_scale, const float* res_shift, float* z, size_t M,
-                     int C, int relu, int groups, void* stream) {
     DVS_REQUIRE(y && stats && fin && z && M > 0 && C > 0 && (C & 3) == 0 && count >= 1 && groups >= 1 && stat_slots >= 1,
                 "dvs_bn_fwd: bad argument");
     DVS_REQUIRE(C / 4 <= NT && (NT % (C / 4)) == 0, "dvs_bn_fwd: C/4 must divide 256 (C=%d)", C);
@@ -736,6 +721,22 @@ inline void bn_reduce_geometry(size_t M, int C, int* blocks, int* rpb) {
     *rpb = r;
     *blocks = (int)((M + r - 1) / r);
 }
+
+// The shape rules every backward entry point shares; `who` names the caller in the message.
+int bn_bwd_shape(const char* who, size_t M, int C, int groups, const float* dgamma_acc, const float* dbeta_acc) {
+    DVS_REQUIRE(M > 0 && C > 0 && (C & 3) == 0 && groups >= 1, "%s: bad argument", who);
+    DVS_REQUIRE(C / 4 <= NT && (NT % (C / 4)) == 0, "%s: C/4 must divide 256 (C=%d)", who, C);
+    DVS_REQUIRE(M < 2147483648ull, "%s: too many rows", who);
+    DVS_REQUIRE((dgamma_acc == nullptr) == (dbeta_acc == nullptr), "%s: gradient sinks come together", who);
+    return DVS_OK;
+}
+
+// Rows of group 0 of a [G][4][C] table (4C floats per group); scale / shift only reach the kernels in the y-mask form.
+struct FinRows {
+    const float *scale, *shift, *mean, *invstd;
+    FinRows(const float* fin, int C, int ymask)
+        : scale(ymask ? fin : nullptr), shift(ymask ? fin + C : nullptr), mean(fin + 2 * C), invstd(fin + 3 * C) {}
+};
 }  // namespace
 
 size_t dvs_bn_bwd_workspace(size_t M, int C, int groups) {
@@ -745,36 +746,19 @@ size_t dvs_bn_bwd_workspace(size_t M, int C, int groups) {
     return (size_t)groups * blocks * 2 * C * sizeof(float);
 }
 
-static int dvs_bn_bwd_reduce_impl(const float* dz, const float* z, const float* y, const float* mean, const float* invstd,
-                                  const float* scale, const float* shift, float* du, float* sums, float* workspace, size_t M, int C,
-                                  int groups, void* stream);
-
-int dvs_bn_bwd_reduce(const float* dz, const float* z, const float* y, const float* mean, const float* invstd,
-                      float* du, float* sums, float* workspace, size_t M, int C, int groups, void* stream) {
-    return dvs_bn_bwd_reduce_impl(dz, z, y, mean, invstd, nullptr, nullptr, du, sums, workspace, M, C, groups, stream);
-}
-
-int dvs_bn_bwd_reduce_ymask(const float* dz, const float* y, const float* mean, const float* invstd, const float* scale,
-                            const float* shift, float* sums, float* workspace, size_t M, int C, int groups, void* stream) {
-    DVS_REQUIRE(scale && shift, "dvs_bn_bwd_reduce_ymask: scale / shift of the forward pass are required");
-    return dvs_bn_bwd_reduce_impl(dz, nullptr, y, mean, invstd, scale, shift, nullptr, sums, workspace, M, C, groups, stream);
-}
-
-static int dvs_bn_bwd_reduce_impl(const float* dz, const float* z, const float* y, const float* mean, const float* invstd,
-                                  const float* scale, const float* shift, float* du, float* sums, float* workspace, size_t M, int C,
-                                  int groups, void* stream) {
-    DVS_REQUIRE(dz && y && mean && invstd && sums && workspace && M > 0 && C > 0 && (C & 3) == 0 && groups >= 1,
-                "dvs_bn_bwd_reduce: bad argument");
-    const int cv = C / 4;
-    DVS_REQUIRE(cv <= NT && (NT % cv) == 0, "dvs_bn_bwd_reduce: C/4 must divide 256 (C=%d)", C);
-    DVS_REQUIRE(M < 2147483648ull, "dvs_bn_bwd_reduce: too many rows");
+int dvs_bn_bwd_reduce(const float* dz, const float* z, const float* y, const float* fin, int ymask, float* du, float* sums,
+                      float* workspace, size_t M, int C, int groups, void* stream) {
+    DVS_REQUIRE(dz && y && fin && sums && workspace, "dvs_bn_bwd_reduce: bad argument");
+    if (int rc = bn_bwd_shape("dvs_bn_bwd_reduce", M, C, groups, nullptr, nullptr)) return rc;
+    DVS_REQUIRE(!(ymask && (z || du)), "dvs_bn_bwd_reduce: the y-mask form neither reads z nor writes du");
+    const FinRows f(fin, C, ymask);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int blocks, rpb;
     bn_reduce_geometry(M, C, &blocks, &rpb);
     {
         dvs::ProfScope prof(dvs::SLOT_BN_BWD, st);
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)blocks, groups), dim3(NT), NT * 8 * sizeof(float), st, dz, z, y, mean,
-                           invstd, scale, shift, du, workspace, (int)M, C, rpb, nullptr);
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)blocks, groups), dim3(NT), NT * 8 * sizeof(float), st, dz, z, y, f.mean,
+                           f.invstd, f.scale, f.shift, du, workspace, (int)M, C, rpb, nullptr);
     }
     // one slice = one ordered sum per address (deterministic mode); 32 slices = 32 float atomics per address
     const int slices = (blocks >= 64 && !dvs::deterministic()) ? 32 : 1, rps = (blocks + slices - 1) / slices;
@@ -783,34 +767,16 @@ static int dvs_bn_bwd_reduce_impl(const float* dz, const float* z, const float* 
     return dvs::check_launch("dvs_bn_bwd_reduce");
 }
 
-static int dvs_bn_bwd_apply_impl(const float* du, const float* y, const float* mean, const float* invstd, const float* gamma,
-                                 const float* sums, float* dy, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups,
-                                 const float* scale, const float* shift, void* stream);
-
-int dvs_bn_bwd_apply(const float* du, const float* y, const float* mean, const float* invstd, const float* gamma,
-                     const float* sums, float* dy, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups,
-                     void* stream) {
-    return dvs_bn_bwd_apply_impl(du, y, mean, invstd, gamma, sums, dy, M, C, dgamma_acc, dbeta_acc, groups, nullptr, nullptr, stream);
-}
-
-int dvs_bn_bwd_apply_ymask(const float* dz, const float* y, const float* mean, const float* invstd, const float* scale,
-                           const float* shift, const float* gamma, const float* sums, float* dy, size_t M, int C, float* dgamma_acc,
-                           float* dbeta_acc, int groups, void* stream) {
-    DVS_REQUIRE(scale && shift, "dvs_bn_bwd_apply_ymask: scale / shift of the forward pass are required");
-    return dvs_bn_bwd_apply_impl(dz, y, mean, invstd, gamma, sums, dy, M, C, dgamma_acc, dbeta_acc, groups, scale, shift, stream);
-}
-
-static int dvs_bn_bwd_apply_impl(const float* du, const float* y, const float* mean, const float* invstd, const float* gamma,
-                                 const float* sums, float* dy, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups,
-                                 const float* scale, const float* shift, void* stream) {
-    DVS_REQUIRE(du && y && mean && invstd && sums && dy && M > 0 && C > 0 && (C & 3) == 0 && groups >= 1, "dvs_bn_bwd_apply: bad argument");
-    DVS_REQUIRE((dgamma_acc == nullptr) == (dbeta_acc == nullptr), "dvs_bn_bwd_apply: gradient sinks come together");
-    DVS_REQUIRE(C / 4 <= NT && (NT % (C / 4)) == 0, "dvs_bn_bwd_apply: C/4 must divide 256 (C=%d)", C);
+int dvs_bn_bwd_apply(const float* du, const float* y, const float* fin, int ymask, const float* gamma, const float* sums, float* dy,
+                     size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups, void* stream) {
+    DVS_REQUIRE(du && y && fin && sums && dy, "dvs_bn_bwd_apply: bad argument");
+    if (int rc = bn_bwd_shape("dvs_bn_bwd_apply", M, C, groups, dgamma_acc, dbeta_acc)) return rc;
+    const FinRows f(fin, C, ymask);
     size_t n4 = M * C / 4;
     hipStream_t st = static_cast<hipStream_t>(stream);
     dvs::ProfScope prof(dvs::SLOT_BN_BWD, st);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4), groups), dim3(NT), 0, st, du, y, mean, invstd, gamma, sums, dy, n4,
-                       C, (float)(1.0 / (double)M), dgamma_acc, dbeta_acc, scale, shift, nullptr, nullptr);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4), groups), dim3(NT), 0, st, du, y, f.mean, f.invstd, gamma, sums, dy, n4,
+                       C, (float)(1.0 / (double)M), dgamma_acc, dbeta_acc, f.scale, f.shift, nullptr, nullptr);
     return dvs::check_launch("dvs_bn_bwd_apply");
 }
 
@@ -818,28 +784,24 @@ int dvs_bn_bwd_slot_floats(int C, int groups) { return (C > 0 && groups > 0) ? g
 
 int dvs_bn_bwd(const float* dz, const float* z, const float* y, const float* fin, int ymask, const float* gamma, float* du, float* dy,
                float* slot_table, float* sums_out, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups, void* stream) {
-    DVS_REQUIRE(dz && y && fin && dy && slot_table && M > 0 && C > 0 && (C & 3) == 0 && groups >= 1, "dvs_bn_bwd: bad argument");
-    const int cv = C / 4;
-    DVS_REQUIRE(cv <= NT && (NT % cv) == 0, "dvs_bn_bwd: C/4 must divide 256 (C=%d)", C);
-    DVS_REQUIRE(M < 2147483648ull, "dvs_bn_bwd: too many rows");
+    DVS_REQUIRE(dz && y && fin && dy && slot_table, "dvs_bn_bwd: bad argument");
+    if (int rc = bn_bwd_shape("dvs_bn_bwd", M, C, groups, dgamma_acc, dbeta_acc)) return rc;
     DVS_REQUIRE(!(ymask && (z || du)), "dvs_bn_bwd: the y-mask form neither reads z nor writes du");
-    DVS_REQUIRE((dgamma_acc == nullptr) == (dbeta_acc == nullptr), "dvs_bn_bwd: gradient sinks come together");
-    const float *scale = fin, *shift = fin + C, *mean = fin + 2 * C, *invstd = fin + 3 * C;     // rows of group 0; 4C per group
+    const FinRows f(fin, C, ymask);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int blocks, rpb;
     bn_reduce_geometry(M, C, &blocks, &rpb);
     {
         dvs::ProfScope prof(dvs::SLOT_BN_BWD, st);
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)blocks, groups), dim3(NT), NT * 8 * sizeof(float), st, dz, z, y, mean,
-                           invstd, ymask ? scale : nullptr, ymask ? shift : nullptr, du, nullptr, (int)M, C, rpb, slot_table);
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)blocks, groups), dim3(NT), NT * 8 * sizeof(float), st, dz, z, y, f.mean,
+                           f.invstd, f.scale, f.shift, du, nullptr, (int)M, C, rpb, slot_table);
     }
     {
         const size_t n4 = M * C / 4;
         dvs::ProfScope prof(dvs::SLOT_BN_BWD, st);
         // the masked gradient: du when the reduce pass wrote it, else dz (masked again from y in the y-mask form, or unmasked: no ReLU)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4), groups), dim3(NT), 0, st, du ? du : dz, y, mean, invstd, gamma,
-                           nullptr, dy, n4, C, (float)(1.0 / (double)M), dgamma_acc, dbeta_acc, ymask ? scale : nullptr,
-                           ymask ? shift : nullptr, slot_table, sums_out);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4), groups), dim3(NT), 0, st, du ? du : dz, y, f.mean, f.invstd, gamma,
+                           nullptr, dy, n4, C, (float)(1.0 / (double)M), dgamma_acc, dbeta_acc, f.scale, f.shift, slot_table, sums_out);
     }
     return dvs::check_launch("dvs_bn_bwd");
 }
@@ -862,12 +824,11 @@ int dvs_bn_relu_maxpool_fwd(const float* y, const float* fin, float* z, float* p
 int dvs_bn_relu_maxpool_bwd(const float* dpool, const unsigned char* idx, const float* dz_extra, const float* y, const float* fin,
                             const float* gamma, float* sums, float* workspace, float* dy, int B, int H, int W, int C,
                             float* dgamma_acc, float* dbeta_acc, int groups, void* stream) {
-    DVS_REQUIRE(dpool && idx && y && fin && sums && workspace && dy && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && groups >= 1 &&
-                    B % groups == 0, "dvs_bn_relu_maxpool_bwd: bad argument");
-    const int cv = C / 4;
-    DVS_REQUIRE(cv <= NT && (NT % cv) == 0, "dvs_bn_relu_maxpool_bwd: C/4 must divide 256 (C=%d)", C);
-    DVS_REQUIRE((dgamma_acc == nullptr) == (dbeta_acc == nullptr), "dvs_bn_relu_maxpool_bwd: gradient sinks come together");
+    DVS_REQUIRE(dpool && idx && y && fin && sums && workspace && dy && B > 0 && H > 0 && W > 0 && groups >= 1 && B % groups == 0,
+                "dvs_bn_relu_maxpool_bwd: bad argument");
     const size_t M = (size_t)(B / groups) * H * W;
+    if (int rc = bn_bwd_shape("dvs_bn_relu_maxpool_bwd", M, C, groups, dgamma_acc, dbeta_acc)) return rc;
+    const int cv = C / 4;
     DVS_REQUIRE((size_t)B * H * W * cv < 2147483648ull, "dvs_bn_relu_maxpool_bwd: too many elements");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t Mb = (size_t)(B / groups) * Ho * Wo;     // 2x2 blocks per group (one per pooled pixel)

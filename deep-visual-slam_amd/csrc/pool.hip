@@ -129,12 +129,8 @@ int dvs_maxpool3x3s2_fwd(const float* x, float* y, unsigned char* idx, int B, in
     return dvs::check_launch("dvs_maxpool3x3s2_fwd");
 }
 
-int dvs_maxpool3x3s2_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C, void* stream) {
-    return dvs_maxpool3x3s2_bwd_res(dy, idx, dx, nullptr, B, H, W, C, stream);
-}
-
-int dvs_maxpool3x3s2_bwd_res(const float* dy, const unsigned char* idx, float* dx, const float* residual, int B, int H, int W,
-                             int C, void* stream) {
+int dvs_maxpool3x3s2_bwd(const float* dy, const unsigned char* idx, float* dx, const float* residual, int B, int H, int W, int C,
+                         void* stream) {
     DVS_REQUIRE(dy && dx && idx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0, "dvs_maxpool3x3s2_bwd: bad argument");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t n = (size_t)B * H * W * (C / 4);

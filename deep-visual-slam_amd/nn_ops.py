@@ -297,8 +297,8 @@ class _MaxPool3x3s2(torch.autograd.Function):
         if dxa is not None:
             dxa = dxa if dxa.is_contiguous(memory_format=cl) else dxa.contiguous(memory_format=cl)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=torch.float32, memory_format=cl)
-        _lib.check(_lib.lib().dvs_maxpool3x3s2_bwd_res(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(),
-                                                       dxa.data_ptr() if dxa is not None else None, B, H, W, C, _lib.stream()),
+        _lib.check(_lib.lib().dvs_maxpool3x3s2_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(),
+                                                   dxa.data_ptr() if dxa is not None else None, B, H, W, C, _lib.stream()),
                    "dvs_maxpool3x3s2_bwd")
         return dx, None
 

@@ -17,6 +17,11 @@
  *     re-entrant and keep no thread-local state besides the error string (the reference's
  *     backward runs on PyTorch's autograd thread);
  *   - sizes are ints; B = batch, H/W = full-resolution image size.
+ *
+ * History
+ *   ABI 12 removes names and adds no capability: where an operation had gained a parameter under a second, suffixed entry
+ *   point (_slots, _ws, _res, _ymask), the full signature now carries the short name and the suffixed twin is gone.  The
+ *   "(ABI n)" marks below say when a capability arrived (5 .. 11: each added entry points or fields and removed none).
  */
 #ifndef DVSLAM_H
 #define DVSLAM_H
@@ -50,7 +55,7 @@ const char* dvs_arch(void);
  * over K with float atomics and the BatchNorm partial sums are added in one fixed order, so a forward pass repeats bit
  * for bit and two runs take the same ReLU / maxpool branches (their gradients then differ by smooth rounding noise only;
  * DESIGN.md section 6).  The BatchNorm batch statistics must then come from dvs_bn_bwd_reduce(dz = y, z = NULL, y,
- * mean = 0, invstd = 1) instead of the convolution's atomic statistics epilogue (the Python side does that). */
+ * a table with mean = 0, invstd = 1) instead of the convolution's atomic statistics epilogue (the Python side does that). */
 int dvs_set_deterministic(int on);
 int dvs_get_deterministic(void);
 
@@ -135,7 +140,7 @@ typedef struct {
                                into w / bias (inference path of model/resnet_encoder.py:100-111) */
     int stat_slots;         /* (ABI 5) 0 / 1: one table; a power of two <= 64: stats is [stat_slots][G][2][Cout] and output tile t
                                adds into copy t % stat_slots -- a 1x1 downsample convolution is all epilogue, and ~900 tiles
-                               adding to the same 2 x Cout addresses serialise in the L2; dvs_bn_fwd_slots adds the copies up.
+                               adding to the same 2 x Cout addresses serialise in the L2; dvs_bn_fwd adds the copies up.
                                Not for the planar (conv1) input. */
 } dvs_conv_fusion;
 
@@ -163,9 +168,14 @@ int dvs_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, 
  *   dvs_wino_weights_batch: both orientations of n weights in one launch; table rows {w, u, u_flip (pointers), Cout, Cin,
  *                         first workgroup, 0 (int32)} sorted by first workgroup, ceil(Cout*Cin/256) workgroups per entry.
  *   dvs_conv3x3_wino_fwd: y [B,H,W,Cout] = [relu](conv3x3(x [B,H,W,Cin]) [+ res] + bias) (res: NULL or a tensor of y's shape -- the
- *                         skip path's gradient when the call is a BasicBlock's conv1 data gradient); stats (NULL = skip) [stat_groups][2][Cout] +=
- *                         per-channel sum / sum of squares of the raw output, as dvs_conv2d_fwd's epilogue does.  Cin % 16 == 0,
- *                         Cout % 4 == 0, tensors < 2 GiB.  as_dgrad: count the launch in the data-gradient profile slot.
+ *                         skip path's gradient when the call is a BasicBlock's conv1 data gradient); stats (NULL = skip)
+ *                         [stat_slots][stat_groups][2][Cout] += per-channel sum / sum of squares of the raw output, as
+ *                         dvs_conv2d_fwd's epilogue does: stat_slots copies of the table (a power of two <= 64, 1 = one table,
+ *                         zero-filled by the caller), workgroup w adds into copy w % stat_slots and dvs_bn_fwd / dvs_bn_finalize
+ *                         add the copies up.  The kernel runs one workgroup per CU whose last act is these atomics; with one
+ *                         copy, thousands of same-address atomics serialise in the L2 and each workgroup's CU waits for them.
+ *                         Cin % 16 == 0, Cout % 4 == 0, tensors < 2 GiB.  as_dgrad: count the launch in the data-gradient
+ *                         profile slot.
  *   dvs_conv3x3_wino_gen: the same kernel behind the decoder's gathers (model/layers.py:26-41 Conv3x3 = ReflectionPad2d(1) + 3x3,
  *                         model/depth_decoder.py:52-62 upsample + concat): logical input [B,H,W,C1+C2] = cat(x [, x2]) where x is
  *                         [B,H/2,W/2,C1] when `upsample` (nearest 2x in the gather) and x2 [B,H,W,C2] the skip (NULL / C2 = 0:
@@ -178,47 +188,37 @@ int dvs_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, 
  *                         one workgroup owns a block).  Cin % 32 == 0, Cout % 32 == 0, tensors < 1 GiB (ABI 7: its offsets carry two mask bits).
  *                         dw may be shared with other launches only through float atomics: with one tile range per block (small
  *                         problems) the kernel adds with plain read-modify-writes, so no OTHER launch may touch the same dw block
- *                         concurrently (one stream per weight tensor, as the Python side keeps it). */
+ *                         concurrently (one stream per weight tensor, as the Python side keeps it).
+ *                         Ordered form (ABI 7): with a partial-sum `workspace` (device, `workspace_bytes` >= what
+ *                         dvs_conv3x3_wino_wgrad_workspace returns for the same sizes) every workgroup stores its 32 x 32 x 9 block
+ *                         there and a second kernel adds the blocks into dw in split order: no float atomics on dw, bit-identical
+ *                         results run to run (the deterministic backward).  workspace = NULL (workspace_bytes 0): the atomic form. */
 int dvs_wino_weights(const float* w, float* u, int Cout, int Cin, int flip, void* stream);
 int dvs_conv3x3_wino_gen(const float* x, const float* x2, const float* u, const float* bias, float* y, int B, int H, int W, int C1, int C2,
                          int Cout, int Ho, int Wo, int org, int upsample, int reflect, int act, int as_dgrad, void* stream);
+size_t dvs_conv3x3_wino_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int target_workgroups);
 int dvs_conv3x3_wino_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int target_workgroups,
-                           void* stream);
+                           float* workspace, size_t workspace_bytes, void* stream);
 /*   dvs_conv3x3_wino_wgrad_gen (ABI 6): the same weight gradient behind the decoder's gathers (the inputs dvs_conv3x3_wino_gen reads
  *   with reflect = 1, org = 1): dw [Cout][3][3][C1+C2] += d/dw of conv3x3(ReflectionPad2d(1)(cat(x [, x2]))) from dy [B,H,W,Cout],
  *   x [B,H/2,W/2,C1] when `upsample` (nearest 2x) else [B,H,W,C1], x2 [B,H,W,C2] the skip (NULL / C2 = 0: none; only with
  *   `upsample`).  dact = 0: dy is the gradient in front of the activation (dvs_act_bwd took the derivative and the bias gradient);
  *   dact = 1 (ReLU) / 2 (ELU): dy is multiplied by act'(y_out) as it is loaded (y_out [B,H,W,Cout] = the forward output) and
  *   dbias [Cout] (NULL: none) += its column sums.  One launch per source, each adding into its channel range of dw.
- *   C1, C2, Cout % 32 == 0, H, W >= 2 (even with `upsample`), tensors < 1 GiB; the same exclusivity rule for dw as above.  Replaces the weight / bias gradient of
- *   model/layers.py:26-41 Conv3x3 (+ ELU of ConvBlock, :106-118) inside model/depth_decoder.py:52-62. */
-int dvs_conv3x3_wino_wgrad_gen(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H, int W,
-                               int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, void* stream);
-/*   Ordered weight gradient (ABI 7): the `_ws` forms take a partial-sum workspace (device, `workspace_bytes` >= what
- *   dvs_conv3x3_wino_wgrad_workspace returns for the same sizes; for the `_gen` form: the larger of its two sources, Cin = max(C1, C2))
- *   -- every workgroup stores its 32 x 32 x 9 block there and a second kernel adds the blocks into dw in split order: no float
- *   atomics on dw, bit-identical results run to run (the deterministic backward).  workspace = NULL: the atomic form above. */
-size_t dvs_conv3x3_wino_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int target_workgroups);
-int dvs_conv3x3_wino_wgrad_ws(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int target_workgroups,
-                              float* workspace, size_t workspace_bytes, void* stream);
-int dvs_conv3x3_wino_wgrad_gen_ws(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H,
-                                  int W, int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, float* workspace,
-                                  size_t workspace_bytes, void* stream);
+ *   C1, C2, Cout % 32 == 0, H, W >= 2 (even with `upsample`), tensors < 1 GiB; the same exclusivity rule for dw as above.
+ *   workspace / workspace_bytes as in dvs_conv3x3_wino_wgrad, sized for the larger of the two sources (Cin = max(C1, C2)).  Replaces
+ *   the weight / bias gradient of model/layers.py:26-41 Conv3x3 (+ ELU of ConvBlock, :106-118) inside model/depth_decoder.py:52-62. */
+int dvs_conv3x3_wino_wgrad_gen(const float* x, const float* x2, const float* dy, const float* y_out, float* dw, float* dbias, int B, int H,
+                               int W, int C1, int C2, int Cout, int upsample, int dact, int target_workgroups, float* workspace,
+                               size_t workspace_bytes, void* stream);
 int dvs_wino_weights_batch(const void* table, int n_entries, int total_workgroups, void* stream);
 int dvs_conv3x3_wino_fwd(const float* x, const float* u, const float* bias, const float* res, float* y, float* stats, int stat_groups,
-                         int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad, void* stream);
-/*   dvs_conv3x3_wino_fwd_slots (ABI 5): the statistics go to `stat_slots` copies of the table, stats = [stat_slots][G][2][Cout]
- *   (power of two <= 64, zero-filled by the caller): workgroup w adds into copy w % stat_slots, and dvs_bn_fwd_slots /
- *   dvs_bn_finalize_slots add the copies up.  The kernel runs one workgroup per CU whose last act is these atomics; with one
- *   copy, thousands of same-address atomics serialise in the L2 and each workgroup's CU waits for them. */
-int dvs_conv3x3_wino_fwd_slots(const float* x, const float* u, const float* bias, const float* res, float* y, float* stats,
-                               int stat_groups, int stat_slots, int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad,
-                               void* stream);
+                         int stat_slots, int B, int H, int W, int Cin, int Cout, int relu, int as_dgrad, void* stream);
 /*   bf16 mode (ABI 8, dvs_set_precision(1)): the stride-1 / zero-pad-1 3x3 convolution on v_mfma_f32_32x32x16_bf16 with the input
  *   patch of a workgroup (8 x 16 output pixels + halo, 64 channels at a time) kept in LDS as bf16 -- every tap reads the same image
  *   (csrc/conv_p16.hip).  dvs_conv3x3_bf16_pack: w fp32 [Cout][3][3][Cin] -> out bf16 [9][K/16][N][16] (9 K N 2 bytes); flip = 0:
  *   K = Cin, N = Cout (forward); flip = 1: K = Cout, N = Cin, taps rotated (data gradient).  dvs_conv3x3_bf16_fwd: y [B,H,W,N] =
- *   conv3x3(x [B,H,W,K]) [+ res]; stats / stat_groups / stat_slots as in dvs_conv3x3_wino_fwd_slots (fp32 sums of the fp32 results);
+ *   conv3x3(x [B,H,W,K]) [+ res]; stats / stat_groups / stat_slots as in dvs_conv3x3_wino_fwd (fp32 sums of the fp32 results);
  *   as_dgrad only labels the profile slot.  K % 64 == 0, N % 64 == 0, tensors < 2 GiB.  Same module as dvs_conv3x3_wino_fwd. */
 /*   dvs_conv3x3_bf16_wgrad: dw [Cout][3][3][Cin] += the weight gradient of that convolution from x [B,H,W,Cin] and dy [B,H,W,Cout], bf16
  *   operands (both k-strided, fetched with ds_read_b64_tr_b16), fp32 accumulation, float atomics into dw (about target_workgroups
@@ -260,49 +260,43 @@ int dvs_act_bwd(const float* dy, const float* y, float* dz, size_t n, int act, f
 int dvs_reflect_fold(const float* g_padded, float* dx, float* dx_skip, int B, int H, int W, int C, int C1, void* stream);
 /*   dx_skip / C1 (upsample+concat forward only, else NULL / 0): the gradient is split in the epilogue --
  *   channels [0,C1) are summed over each 2x2 block into dx = [B,H/2,W/2,C1] with atomics (caller zero-fills dx),
- *   channels [C1,Cin) are stored to dx_skip = [B,H,W,Cin-C1]; C1 == Cin (upsample only) needs no dx_skip. */
-int dvs_conv2d_dgrad(const float* dy, const float* wt, float* dx, const dvs_conv_desc* d, const float* y_out,
-                     int dact, float* dx_skip, int C1, void* stream);
-/*   dvs_conv2d_dgrad_res (ABI 5): dx = data gradient + residual [B,H,W,Cin] (NULL = none; C1 must be 0).  Where a tensor feeds
+ *   channels [C1,Cin) are stored to dx_skip = [B,H,W,Cin-C1]; C1 == Cin (upsample only) needs no dx_skip.
+ *   residual (ABI 5; NULL = none; C1 must be 0): dx = data gradient + residual [B,H,W,Cin].  Where a tensor feeds
  *   several consumers -- a BasicBlock input read by conv1, the 1x1 downsample branch and, in DepthNet, the decoder's skip
  *   connection (torchvision BasicBlock through model/resnet_encoder.py:94-111, model/depthnet.py:79-85) -- autograd would add
  *   the consumers' gradients in one more pass over the tensor each; the gradient already computed is added in this kernel's
- *   epilogue instead.  Same for dvs_conv2d_head_bwd_res (dx += dx_residual) and dvs_maxpool3x3s2_bwd_res below. */
-int dvs_conv2d_dgrad_res(const float* dy, const float* wt, float* dx, const dvs_conv_desc* d, const float* y_out,
-                         int dact, float* dx_skip, int C1, const float* residual, void* stream);
-int dvs_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d,
-                     const dvs_conv_fusion* f, const float* y_out, int dact, void* stream);
-/*   Ordered form (ABI 7): with a slab workspace of >= dvs_conv2d_wgrad_workspace(...) bytes every workgroup of the split-K implicit
- *   GEMM stores its partial tile with plain stores and a second kernel adds the splits into dw in split order -- no float atomics
- *   on dw (they run at a fifth of the plain-store rate on this chip and make the result depend on timing).  The stem and the thin
- *   full-resolution decoder layers have no slab path (workspace size 0: the call behaves like dvs_conv2d_wgrad); a bias gradient
- *   (dbias) still rides on atomics.  workspace = NULL: dvs_conv2d_wgrad. */
+ *   epilogue instead.  Same for dvs_conv2d_head_bwd (dx_residual) and dvs_maxpool3x3s2_bwd (residual) below. */
+int dvs_conv2d_dgrad(const float* dy, const float* wt, float* dx, const dvs_conv_desc* d, const float* y_out,
+                     int dact, float* dx_skip, int C1, const float* residual, void* stream);
+/*   dvs_conv2d_wgrad, ordered form (ABI 7): with a slab workspace of >= dvs_conv2d_wgrad_workspace(...) bytes every workgroup of the
+ *   split-K implicit GEMM stores its partial tile with plain stores and a second kernel adds the splits into dw in split order -- no
+ *   float atomics on dw (they run at a fifth of the plain-store rate on this chip and make the result depend on timing).  The stem
+ *   and the thin full-resolution decoder layers have no slab path (workspace size 0: the workspace is ignored); a bias gradient
+ *   (dbias) still rides on atomics.  workspace = NULL (workspace_bytes 0): the atomic form. */
 size_t dvs_conv2d_wgrad_workspace(const dvs_conv_desc* d, const dvs_conv_fusion* f, int dact, int with_bias);
-int dvs_conv2d_wgrad_ws(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d, const dvs_conv_fusion* f,
-                        const float* y_out, int dact, float* workspace, size_t workspace_bytes, void* stream);
+int dvs_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias, const dvs_conv_desc* d, const dvs_conv_fusion* f,
+                     const float* y_out, int dact, float* workspace, size_t workspace_bytes, void* stream);
 
 /* Narrow output heads (Cout in {1,2,6,8}, Cin % 4 == 0, stride 1, "same" size: 2*pad == k-1) on the vector
  * ALUs: DepthNet's dispconv layers (model/depthnet.py:57-58,86-88) and PoseNet's last 1x1
  * (model/posenet_single.py:165).  `act` as in dvs_conv_fusion.  bwd: dx (NULL = skip), dw/dbias accumulated
- * with atomics (caller zero-fills); y / dy are the forward output and its gradient. */
+ * with atomics (caller zero-fills); y / dy are the forward output and its gradient; dx_residual (NULL = none; needs dx):
+ * dx = data gradient + dx_residual [B,H,W,Cin]. */
 int dvs_conv2d_head_fwd(const float* x, const float* w, const float* bias, float* y, const dvs_conv_desc* d, int act,
                         void* stream);
 int dvs_conv2d_head_bwd(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
-                        float* dbias, const dvs_conv_desc* d, int act, void* stream);
-int dvs_conv2d_head_bwd_res(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw,
-                            float* dbias, const dvs_conv_desc* d, int act, const float* dx_residual, void* stream);
+                        float* dbias, const dvs_conv_desc* d, int act, const float* dx_residual, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a1  the ResNet stem's MaxPool2d(kernel_size=3, stride=2, padding=1) on NHWC tensors
  *     (torchvision resnet18.maxpool reached through model/resnet_encoder.py:104).
  *     x, dx: [B,H,W,C]; y, dy: [B,Ho,Wo,C] with Ho = (H-1)/2+1; idx: [B,Ho,Wo,C] bytes, the winning tap
- *     ky*3+kx (first maximum in scan order, as torch); C % 4 == 0.  bwd writes every element of dx.
+ *     ky*3+kx (first maximum in scan order, as torch); C % 4 == 0.  bwd writes every element of dx:
+ *     dx = maxpool gradient + residual [B,H,W,C] (NULL = none): the stem output feeds the pool and DepthNet's finest skip.
  * ------------------------------------------------------------------------------------------- */
 int dvs_maxpool3x3s2_fwd(const float* x, float* y, unsigned char* idx, int B, int H, int W, int C, void* stream);
-int dvs_maxpool3x3s2_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C, void* stream);
-/* dx = maxpool gradient + residual [B,H,W,C] (NULL = none): the stem output feeds the pool and DepthNet's finest skip. */
-int dvs_maxpool3x3s2_bwd_res(const float* dy, const unsigned char* idx, float* dx, const float* residual, int B, int H, int W,
-                             int C, void* stream);
+int dvs_maxpool3x3s2_bwd(const float* dy, const unsigned char* idx, float* dx, const float* residual, int B, int H, int W, int C,
+                         void* stream);
 /* `upsample` of model/layers.py:196-199 (F.interpolate(scale_factor=2, mode="nearest")) as a standalone operator on NHWC
  * tensors: x, dx [B,H,W,C]; y, dy [B,2H,2W,C]; C % 4 == 0.  The backward is the 2x2 block sum.  (The decoder itself never
  * materialises the upsampled tensor: dvs_conv_fusion.x2 / C1 gather it inside the convolution.) */
@@ -311,70 +305,71 @@ int dvs_upsample2x_bwd(const float* dy, float* dx, int B, int H, int W, int C, v
 
 /* ---------------------------------------------------------------------------------------------
  * a1  training-mode BatchNorm2d (+ residual add, + ReLU) of the ResNet BasicBlocks on NHWC tensors
- *     (torchvision BasicBlock tail used by model/resnet_encoder.py:100-111).  `stats` = [2][C] per-channel
- *     sum / sum of squares of y as accumulated by dvs_conv2d_fwd's epilogue; count = B*H*W.
- *       finalize : mean, invstd = rsqrt(biased var + eps); scale = gamma*invstd; shift = beta - mean*scale;
+ *     (torchvision BasicBlock tail used by model/resnet_encoder.py:100-111).
+ *
+ *     Shapes.  M = pixels (rows) per group, C % 4 == 0 and C/4 divides 256 (C in {4, 8, 16 .. 1024}).  groups G >= 1 (PoseNet
+ *     evaluates its two frame pairs as one batch, each half normalised on its own): ONE launch serves G independent
+ *     sub-batches of M rows each, stored back to back -- tensors [G*M][C], sums [G][2][C].  gamma / beta / running statistics /
+ *     gradient sinks are shared by the groups (running statistics get the G updates in order).
+ *     `stats` = [stat_slots][G][2][C]: per-channel sum / sum of squares of y as accumulated by the producing convolution's
+ *     epilogue (dvs_conv2d_fwd, dvs_conv3x3_wino_fwd), stat_slots >= 1 copies that are added up on load; count = M.
+ *     `fin` = [G][4][C]: rows scale, shift, mean, invstd of every group -- written by the forward, read by the backward.
+ *
+ *     Forward.
+ *       finalize : mean, invstd = rsqrt(biased var + eps); scale = gamma*invstd; shift = beta - mean*scale, written to the
+ *                  group-0 rows scale / shift / mean / invstd of a [G][4][C] table (group g at + g*4*C);
  *                  running_mean/var updated with `momentum` (unbiased var), NULL = leave them;
  *                  *num_batches_tracked (int64, NULL = skip) is incremented, as nn.BatchNorm2d does.
- *       apply_fwd: z = [relu](y*scale + shift [+ residual | + residual*res_scale + res_shift]).
- *       bwd_reduce: du = dz * [z > 0] (z NULL = no ReLU; du NULL = do not store); sums[0][c] += sum du,
- *                  sums[1][c] += sum du * xhat (= d beta, d gamma); caller zero-fills sums.  Each workgroup
- *                  writes one partial row into `workspace` (dvs_bn_bwd_workspace bytes), a second small
- *                  kernel adds the rows into sums (same-address float atomics serialise at ~85 ns each).
- *       bwd_apply: dy = gamma * invstd * (du - sums0/M - xhat * sums1/M); dgamma_acc / dbeta_acc (both or
- *                  neither, NULL = skip): d gamma += sums1, d beta += sums0, i.e. the parameter gradients are
- *                  accumulated in place (what autograd's AccumulateGrad would do with one more launch each).
- *     M = pixels (rows), C % 4 == 0 and C/4 divides 256 (C in {4, 8, 16 .. 1024}).
- *     groups G >= 1 (PoseNet evaluates its two frame pairs as one batch, each half normalised on its own): ONE launch
- *     serves G independent sub-batches of M rows each, stored back to back -- tensors [G*M][C], stats / sums [G][2][C],
- *     scale / shift / mean / invstd = rows of a [G][4][C] table (pass the group-0 rows); gamma / beta / running
- *     statistics / gradient sinks are shared (running statistics get the G updates in order).
+ *       apply_fwd: z = [relu](y*scale + shift [+ residual | + residual*res_scale + res_shift]); scale / shift (and res_scale /
+ *                  res_shift) = group-0 rows of a [G][4][C] table.
+ *       fwd      : finalize + apply_fwd in ONE launch (what the training forward uses); `fin` out; res_scale / res_shift =
+ *                  group-0 rows of the downsample branch's own table, produced by dvs_bn_finalize.
+ *
+ *     Backward, two passes over the tensors.
+ *       bwd_reduce: du = dz * mask (du NULL = do not store); sums[0][c] += sum du, sums[1][c] += sum du * xhat (= d beta,
+ *                  d gamma); caller zero-fills sums.  Each workgroup writes one partial row into `workspace`
+ *                  (dvs_bn_bwd_workspace bytes; 0 = unsupported shape), a second small kernel adds the rows into sums
+ *                  (same-address float atomics serialise at ~85 ns each; one ordered sum under dvs_set_deterministic).
+ *       bwd_apply: dy = gamma * invstd * (du - sums0/M - xhat * sums1/M); dgamma_acc / dbeta_acc (both or neither, NULL =
+ *                  skip): d gamma += sums1, d beta += sums0, i.e. the parameter gradients are accumulated in place (what
+ *                  autograd's AccumulateGrad would do with one more launch each).
+ *       The mask: ymask == 0: [z > 0] (z NULL = no ReLU, no mask); rows 0 / 1 of `fin` are not read.  ymask != 0: ReLU without a
+ *       residual (bn1 of a BasicBlock, the stem): z > 0 is recomputed from y with the forward's own expression
+ *       max(y*scale + shift, 0), so the backward neither reads z nor writes / re-reads du (both must be NULL in bwd_reduce):
+ *       5 tensor passes instead of 7; bwd_apply is handed dz in du's place and masks it again.
+ *       A caller without a forward table builds one: (mean, invstd) = (0, 1) makes bwd_reduce a plain column sum of dz and
+ *       dz * y (the deterministic batch statistics; the eval-mode affine map's parameter gradients).
+ *       bwd      : (ABI 5) reduce + apply without the kernel in between that adds the per-workgroup partial rows: `slot_table` =
+ *                  dvs_bn_bwd_slot_floats(C, groups) zero-filled floats ([G][32][2][C]); workgroup w of the reduce pass adds its
+ *                  partial sums into copy w % 32 and every workgroup of the apply pass adds the copies up.  z / du / ymask as
+ *                  above.  sums_out (NULL = skip): [G][2][C] = sum(du), sum(du * xhat) for callers that hand d beta / d gamma
+ *                  to autograd.  The deterministic mode keeps bwd_reduce / bwd_apply with their ordered sum.
+ *
+ *     Stem tail (ABI 5): relu(bn1(conv1(x))) -> MaxPool2d(3, 2, 1) of model/resnet_encoder.py:102-104 without the tensor in between.
+ *       relu_maxpool_fwd: y [B,H,W,C] = raw conv1 output, fin from dvs_bn_finalize (group = image / (B/G)); pooled [B,Ho,Wo,C]
+ *                  and idx (one byte per element, winning tap ky*3+kx, first maximum in scan order) as dvs_maxpool3x3s2_fwd
+ *                  would give on z = relu(y*scale+shift); z [B,H,W,C] is written only when non-NULL (DepthNet's finest skip
+ *                  connection reads it; PoseNet never does).
+ *       relu_maxpool_bwd: dz = maxpool gradient (gathered from dpool / idx, never stored) + dz_extra (NULL or [B,H,W,C]: the
+ *                  gradient of z's other consumer), ReLU mask recomputed from y; sums [G][2][C] receive sum(dz), sum(dz*xhat)
+ *                  (written, not accumulated); dy [B,H,W,C] = training-mode BatchNorm backward; dgamma_acc / dbeta_acc as in
+ *                  bwd_apply.  workspace: dvs_bn_bwd_slot_floats(C, G) ZERO-FILLED floats (the slot table of bwd).
  * ------------------------------------------------------------------------------------------- */
-int dvs_bn_finalize(const float* stats, double count, const float* gamma, const float* beta, float* running_mean,
+int dvs_bn_finalize(const float* stats, int stat_slots, double count, const float* gamma, const float* beta, float* running_mean,
                     float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
                     float* invstd, int C, long long* num_batches_tracked, int groups, void* stream);
-/* finalize + apply_fwd in ONE launch (what the training forward uses): `stats` [G][2][C] raw sums from the conv epilogue,
- * `fin` [G][4][C] out (scale, shift, mean, invstd: kept for the backward); residual / res_scale / res_shift as in
- * dvs_bn_apply_fwd (res_scale / res_shift = group-0 rows of the downsample branch's own [G][4][C] table, produced by
- * dvs_bn_finalize). */
-int dvs_bn_fwd(const float* y, const float* stats, double count, const float* gamma, const float* beta,
-               float* running_mean, float* running_var, float momentum, float eps, long long* num_batches_tracked,
-               float* fin, const float* residual, const float* res_scale, const float* res_shift, float* z, size_t M,
-               int C, int relu, int groups, void* stream);
-/* the same with `stats` = [stat_slots][G][2][C]: copies that are added up on load (dvs_conv3x3_wino_fwd_slots) */
-int dvs_bn_fwd_slots(const float* y, const float* stats, int stat_slots, double count, const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, long long* num_batches_tracked,
-                     float* fin, const float* residual, const float* res_scale, const float* res_shift, float* z, size_t M,
-                     int C, int relu, int groups, void* stream);
-int dvs_bn_finalize_slots(const float* stats, int stat_slots, double count, const float* gamma, const float* beta, float* running_mean,
-                          float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
-                          float* invstd, int C, long long* num_batches_tracked, int groups, void* stream);
 int dvs_bn_apply_fwd(const float* y, const float* scale, const float* shift, const float* residual,
                      const float* res_scale, const float* res_shift, float* z, size_t M, int C, int relu, int groups,
                      void* stream);
-/* bytes of the per-workgroup partial-sum workspace of dvs_bn_bwd_reduce (0 = unsupported shape) */
+int dvs_bn_fwd(const float* y, const float* stats, int stat_slots, double count, const float* gamma, const float* beta,
+               float* running_mean, float* running_var, float momentum, float eps, long long* num_batches_tracked,
+               float* fin, const float* residual, const float* res_scale, const float* res_shift, float* z, size_t M,
+               int C, int relu, int groups, void* stream);
 size_t dvs_bn_bwd_workspace(size_t M, int C, int groups);
-int dvs_bn_bwd_reduce(const float* dz, const float* z, const float* y, const float* mean, const float* invstd,
-                      float* du, float* sums, float* workspace, size_t M, int C, int groups, void* stream);
-int dvs_bn_bwd_apply(const float* du, const float* y, const float* mean, const float* invstd, const float* gamma,
-                     const float* sums, float* dy, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups,
-                     void* stream);
-/* Stem tail (ABI 5): relu(bn1(conv1(x))) -> MaxPool2d(3, 2, 1) of model/resnet_encoder.py:102-104 without the tensor in between.
- *   fwd: y [B,H,W,C] = raw conv1 output, fin [G][4][C] = scale, shift, mean, invstd from dvs_bn_finalize (group = image / (B/G));
- *        pooled [B,Ho,Wo,C] and idx (one byte per element, winning tap ky*3+kx, first maximum in scan order) as
- *        dvs_maxpool3x3s2_fwd would give on z = relu(y*scale+shift); z [B,H,W,C] is written only when non-NULL (DepthNet's
- *        finest skip connection reads it; PoseNet never does).
- *   bwd: dz = maxpool gradient (gathered from dpool / idx, never stored) + dz_extra (NULL or [B,H,W,C]: the gradient of z's
- *        other consumer), ReLU mask recomputed from y; sums [G][2][C] receive sum(dz), sum(dz*xhat);
- *        dy [B,H,W,C] = training-mode BatchNorm backward; dgamma_acc / dbeta_acc as in dvs_bn_bwd_apply.  workspace:
- *        dvs_bn_bwd_slot_floats(C, G) ZERO-FILLED floats (the slot table of dvs_bn_bwd); sums [G][2][C] is written, not
- *        accumulated.  C/4 must divide 256. */
-/* (ABI 5) reduce + apply without the kernel in between that adds the per-workgroup partial rows: `slot_table` =
- *   dvs_bn_bwd_slot_floats(C, groups) zero-filled floats ([G][32][2][C]); workgroup w of the reduce pass adds its partial sums into
- *   copy w % 32 and every workgroup of the apply pass adds the copies up.  fin = the forward's [G][4][C] table.  ymask != 0: ReLU
- *   without a residual, the mask recomputed from y (z and du must be NULL); else z (NULL = no ReLU) masks dz and du (NULL = not
- *   needed) receives dz * [z > 0].  sums_out (NULL = skip): [G][2][C] = sum(du), sum(du * xhat) for callers that hand d beta /
- *   d gamma to autograd.  The deterministic mode (dvs_set_deterministic) keeps dvs_bn_bwd_reduce / _apply with their ordered sum. */
+int dvs_bn_bwd_reduce(const float* dz, const float* z, const float* y, const float* fin, int ymask, float* du, float* sums,
+                      float* workspace, size_t M, int C, int groups, void* stream);
+int dvs_bn_bwd_apply(const float* du, const float* y, const float* fin, int ymask, const float* gamma, const float* sums, float* dy,
+                     size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups, void* stream);
 int dvs_bn_bwd_slot_floats(int C, int groups);
 int dvs_bn_bwd(const float* dz, const float* z, const float* y, const float* fin, int ymask, const float* gamma, float* du, float* dy,
                float* slot_table, float* sums_out, size_t M, int C, float* dgamma_acc, float* dbeta_acc, int groups, void* stream);
@@ -383,14 +378,6 @@ int dvs_bn_relu_maxpool_fwd(const float* y, const float* fin, float* z, float* p
 int dvs_bn_relu_maxpool_bwd(const float* dpool, const unsigned char* idx, const float* dz_extra, const float* y, const float* fin,
                             const float* gamma, float* sums, float* workspace, float* dy, int B, int H, int W, int C,
                             float* dgamma_acc, float* dbeta_acc, int groups, void* stream);
-/* ReLU without a residual (bn1 of a BasicBlock, the stem): the mask z > 0 is recomputed from y with the forward's own
- * expression max(y*scale + shift, 0) (scale / shift = rows 0 / 1 of dvs_bn_fwd's `fin` table), so the backward neither reads z
- * nor writes / re-reads du: 5 tensor passes instead of 7.  `dz` takes du's place in the apply call. */
-int dvs_bn_bwd_reduce_ymask(const float* dz, const float* y, const float* mean, const float* invstd, const float* scale,
-                            const float* shift, float* sums, float* workspace, size_t M, int C, int groups, void* stream);
-int dvs_bn_bwd_apply_ymask(const float* dz, const float* y, const float* mean, const float* invstd, const float* scale,
-                           const float* shift, const float* gamma, const float* sums, float* dy, size_t M, int C, float* dgamma_acc,
-                           float* dbeta_acc, int groups, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a4  axis-angle + translation -> 4x4 camera motion

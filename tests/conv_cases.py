@@ -153,7 +153,7 @@ def thin_wgrad(cfg, batch):
 
 
 def thin_dgrad(cfg, batch, residual=False):
-    """csrc/conv_thin.hip thin_dgrad as dvs_conv2d_dgrad_res reaches it (reflection pad, no residual)."""
+    """csrc/conv_thin.hip thin_dgrad as dvs_conv2d_dgrad reaches it (reflection pad, no residual)."""
     B, ci, H, W, c1, up = _logical(cfg, batch)
     co, split = cfg["w"][0], (c1 if up else 0)
     if not _thin_common(cfg) or residual or H < 8 or (split and (H | W) & 1):

@@ -54,7 +54,7 @@ def test_new_symbols_are_exported_and_declared(built):
         assert hasattr(l, name), name
         assert name in built.exported_symbols(), name
         assert re.search(r"\b" + name + r"\s*\(", src), name
-    assert built.ABI_VERSION == 11 and l.dvs_abi_version() == 11
+    assert built.ABI_VERSION == 12 and l.dvs_abi_version() == 12
 
 
 def _cfg(built, B, Cn, H, W, L, r):

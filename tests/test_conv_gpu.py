@@ -171,7 +171,7 @@ def test_head_conv(gpu_device, cin, cout, k, refl, act, H, W):
         assert a.shape == r.shape and relmax(a, r) < 1e-4, (nm, relmax(a, r))
 
 
-# ---- fan-in gradients added inside the data-gradient kernels (dvs_conv2d_dgrad_res / _head_bwd_res / maxpool _bwd_res)
+# ---- fan-in gradients added inside the data-gradient kernels (the residual arguments of dvs_conv2d_dgrad / _head_bwd / dvs_maxpool3x3s2_bwd)
 RES_CASES = [
     # name, B, Cin, Cout, k, stride, pad, H, W      (the encoder's consumers of a block input / feature map)
     ("3x3_s2", 2, 64, 128, 3, 2, 1, 24, 40),        # conv1 of a downsample block

@@ -107,7 +107,7 @@ def test_new_symbols_are_exported_and_declared(built):
     for name in NEW:
         assert hasattr(l, name) and name in built.exported_symbols(), name
         assert re.search(r"\b" + name + r"\s*\(", src), name
-    assert built.ABI_VERSION == 11 and l.dvs_abi_version() == 11
+    assert built.ABI_VERSION == 12 and l.dvs_abi_version() == 12
     assert l.dvs_inorm_slice_pixels() == 1024
 
 

@@ -1,5 +1,5 @@
 """Ordered (slab / workspace) weight gradients -- the deterministic backward of the two big weight-gradient kernel families:
-the Winograd kernel (dvs_conv3x3_wino_wgrad_ws / _gen_ws) and the split-K implicit GEMM (dvs_conv2d_wgrad_ws).  Each must (1) agree
+the Winograd kernel (dvs_conv3x3_wino_wgrad / _gen) and the split-K implicit GEMM (dvs_conv2d_wgrad), each given a workspace.  Each must (1) agree
 with the atomic form and with torch's fp64 gradient to the tolerance of the atomic kernels' own tests (1e-4 of the tensor max)
 and (2) repeat BIT FOR BIT, which the atomic form does not promise.  Reference arithmetic: the weight gradient of nn.Conv2d as
 used by torchvision's BasicBlock (model/resnet_encoder.py:83-111) and Conv3x3 (model/layers.py:26-41)."""
@@ -96,7 +96,7 @@ def test_workspace_query_and_short_workspace(gpu_device):
     dy = torch.randn(2, 64, 24, 32, device=gpu_device).contiguous(memory_format=CL)
     dw = torch.zeros(64, 64, 3, 3, device=gpu_device).contiguous(memory_format=CL)
     ws = torch.empty(16, device=gpu_device)
-    rc = l.dvs_conv3x3_wino_wgrad_ws(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), 2, 24, 32, 64, 64, 0, ws.data_ptr(), 64, _lib.stream())
+    rc = l.dvs_conv3x3_wino_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), 2, 24, 32, 64, 64, 0, ws.data_ptr(), 64, _lib.stream())
     assert rc < 0 and b"workspace" in l.dvs_last_error()
     d = DC._desc(2, 64, 24, 32, (128, 64, 3, 3), 2, 1, False)
     f = DC._fusion(x, None, None, None, False, False)

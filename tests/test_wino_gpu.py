@@ -400,7 +400,7 @@ def test_bias_relu_layer_autograd_matches_torch(B, c, h, w):
 
 @pytest.mark.parametrize("B,c,h,w,groups", [(4, 64, 60, 80, 1), (4, 64, 60, 80, 2), (2, 128, 13, 27, 1)])
 def test_statistics_spread_over_slots(B, c, h, w, groups):
-    """dvs_conv3x3_wino_fwd_slots: the workgroups add their BatchNorm statistics into 16 copies of the table (one workgroup per CU
+    """dvs_conv3x3_wino_fwd with stat_slots = 16: the workgroups add their BatchNorm statistics into 16 copies of the table (one workgroup per CU
     ends with these atomics; on ONE copy they serialise); the copies add up to the sums, and bn.bn_act consumes the copies."""
     import torch.nn as nn
     from deep_visual_slam_amd import bn as DB, conv as DC

@@ -21,8 +21,8 @@ for cin, H, W in ((16, 480, 640), (32, 240, 320), (64, 120, 160), (128, 60, 80))
     dw, db = torch.zeros_like(w), torch.zeros_like(b)
 
     def run():
-        check(_lib.lib().dvs_conv2d_head_bwd_res(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), None, dw.data_ptr(), db.data_ptr(),
-                                                 C.byref(d), ACT["sigmoid"], None, _lib.stream()), "dvs_conv2d_head_bwd")
+        check(_lib.lib().dvs_conv2d_head_bwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), None, dw.data_ptr(), db.data_ptr(),
+                                             C.byref(d), ACT["sigmoid"], None, _lib.stream()), "dvs_conv2d_head_bwd")
     run()
     torch.cuda.synchronize()
     wr = w.clone().requires_grad_(True)
@@ -44,8 +44,8 @@ for cin, H, W in ((16, 480, 640), (32, 240, 320), (64, 120, 160), (128, 60, 80))
     dx = torch.empty_like(x)
 
     def bwd():
-        check(_lib.lib().dvs_conv2d_head_bwd_res(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                                 C.byref(d), ACT["sigmoid"], None, _lib.stream()), "dvs_conv2d_head_bwd")
+        check(_lib.lib().dvs_conv2d_head_bwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                             C.byref(d), ACT["sigmoid"], None, _lib.stream()), "dvs_conv2d_head_bwd")
     xr = x.clone().requires_grad_(True)
     (gx,) = torch.autograd.grad(torch.sigmoid(F.conv2d(F.pad(xr, (1,) * 4, mode="reflect"), w, b)), [xr], dy)
     for _ in range(3):

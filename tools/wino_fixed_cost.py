@@ -17,7 +17,7 @@ for name, co, h, w in (("l1 <2,2>", 64, 120, 160), ("l2 <1,4>", 128, 60, 80), ("
         y = torch.empty((B, co, h, w), device=dev).contiguous(memory_format=CL)
         stt = torch.zeros(16, 1, 2, co, device=dev)
         def go():
-            l.dvs_conv3x3_wino_fwd_slots(x.data_ptr(), u.data_ptr(), None, None, y.data_ptr(), stt.data_ptr(), 1, 16, B, h, w, ci, co, 0, 0, st)
+            l.dvs_conv3x3_wino_fwd(x.data_ptr(), u.data_ptr(), None, None, y.data_ptr(), stt.data_ptr(), 1, 16, B, h, w, ci, co, 0, 0, st)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(5): go()
         e0.record()
