@@ -182,6 +182,10 @@ _SIGNATURES = {
     "dvs_inorm_bwd": (C.c_int, [_vp] * 7 + [C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_upflow8_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "dvs_upflow8_bwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_pool_fc_slice_pixels": (C.c_int, []),
+    "dvs_pool_fc_workspace": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
+    "dvs_pool_fc_fwd": (C.c_int, [_vp] * 6 + [C.c_size_t, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
+    "dvs_pool_fc_bwd": (C.c_int, [_vp] * 7 + [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
 }
 
 _lib = None

@@ -762,6 +762,33 @@ int dvs_inorm_bwd(const float* dout, const float* y, const float* out, const flo
 int dvs_upflow8_fwd(const float* flow, float* out, int N, int h, int w, int flow_nchw, void* stream);
 int dvs_upflow8_bwd(const float* dout, float* dflow, int N, int h, int w, int dflow_nchw, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) FlowPoseNet's pooling head
+ *     replaces nn.ReLU, nn.AdaptiveAvgPool2d(1), self.fc and * self.pose_scale, model/posenet_single.py:116-122 and 137-142
+ *
+ *   y [N][P][C] fp32: the NHWC memory of the last regressor convolution, P = h * w; W [J][C]; b [J] or NULL.
+ *       a(v)        = relu ? max(v, 0) : v
+ *       mean[n][c]  = (1/P) sum_p a(y[n][p][c])                          [N][C], kept for the backward
+ *       out[n][j]   = scale * (b[j] + sum_c W[j][c] * mean[n][c])        [N][J]
+ *   dvs_pool_fc_bwd: for dout = dL/dout [N][J]
+ *       g[n][c]     = (scale/P) sum_j dout[n][j] * W[j][c]
+ *       dy[n][p][c] = g[n][c] * (relu ? [y > 0] : 1)                     y == 0 gives 0, as torch does
+ *       dW[j][c]    = scale * sum_n dout[n][j] * mean[n][c]              written, not accumulated
+ *       db[j]       = scale * sum_n dout[n][j]                           db == NULL: not computed
+ *   Per slice of dvs_pool_fc_slice_pixels() = 256 pixels one mean per channel (workspace [N][S][C]); a second launch folds the
+ *       slice means in ascending order and computes the J dot products by a fixed tree.  No atomics, a fixed order: bit-reproducible,
+ *       and a sample's out, mean and dy do not depend on the other samples of the batch.
+ *   C % 4 == 0 (4 .. 1024), 1 <= J <= 16, 1 <= N <= 65535, 1 <= P < 2^31; 16-byte aligned pointers.
+ *   workspace: dvs_pool_fc_workspace(N, P, C) bytes (0 for invalid arguments), device memory, needed by the forward only.
+ *   DVS_ERR_INVALID, before any launch, for a null or misaligned pointer, C, J, N or P out of range, a workspace that is too small.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_pool_fc_slice_pixels(void);                                      /* model/posenet_single.py:117 */
+size_t dvs_pool_fc_workspace(int N, long long P, int C);                 /* model/posenet_single.py:117 */
+int dvs_pool_fc_fwd(const float* y, const float* W, const float* b, float* out, float* mean, void* workspace, size_t workspace_bytes,
+                    int N, long long P, int C, int J, int relu, float scale, void* stream);   /* model/posenet_single.py:137-142 */
+int dvs_pool_fc_bwd(const float* dout, const float* y, const float* mean, const float* W, float* dy, float* dW, float* db, int N,
+                    long long P, int C, int J, int relu, float scale, void* stream);   /* autograd of model/posenet_single.py:137-142 */
+
 #ifdef __cplusplus
 }
 #endif
