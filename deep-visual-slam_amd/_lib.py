@@ -186,6 +186,11 @@ _SIGNATURES = {
     "dvs_pool_fc_workspace": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
     "dvs_pool_fc_fwd": (C.c_int, [_vp] * 6 + [C.c_size_t, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
     "dvs_pool_fc_bwd": (C.c_int, [_vp] * 7 + [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
+    "dvs_convex_up_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dvs_convex_up_fwd": (C.c_int, [_vp] * 3 + [C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
+    "dvs_convex_up_bwd": (C.c_int, [_vp] * 6 + [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
+    "dvs_shift_stack_fwd": (C.c_int, [_vp, _vp] + [C.c_int] * 5 + [_vp]),
+    "dvs_shift_stack_bwd": (C.c_int, [_vp, _vp] + [C.c_int] * 5 + [_vp]),
 }
 
 _lib = None

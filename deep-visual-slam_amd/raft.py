@@ -1,5 +1,6 @@
-"""SmallRAFT end to end on the device (model/raft/core/raft.py:23-119): the two encoders (raft_encoder), the correlation block
-(raft_corr), the update block (raft_update) and upflow8 (csrc/upflow.hip).
+"""SmallRAFT and RAFT end to end on the device (model/raft/core/raft.py:23-119 and 122-244): the two encoders (raft_encoder), the
+correlation block (raft_corr), the update block (raft_update), upflow8 (csrc/upflow.hip) and, for the full-size model, the convex
+upsampling upsample_flow (csrc/convexup.hip); RAFT's own usage is in its docstring.
 
     raft = SmallRAFT(); raft.load_state_dict(torch.load("raft-small.pth")); raft = raft.cuda()
     flows = raft(image1, image2, iters=12)              # list of 12 [B,2,H,W] flows, images in 0 .. 1
@@ -18,8 +19,8 @@ import torch.nn as nn
 from . import _lib, conv
 from ._lib import DvsError, check
 from .raft_corr import AlternateCorrBlock, CorrBlock
-from .raft_encoder import SmallEncoder
-from .raft_update import SmallUpdateBlock
+from .raft_encoder import BasicEncoder, SmallEncoder
+from .raft_update import BasicUpdateBlock, SmallUpdateBlock
 
 CL = torch.channels_last
 
@@ -81,14 +82,174 @@ def _option(args, name, default):
     return getattr(args, name, default)
 
 
-class RAFT(nn.Module):
-    """The full-size model (raft.py:122-244) is not built: BasicEncoder, SepConvGRU and the convex-upsampling mask head are missing."""
+class _ConvexUp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, mask, mask_scale):
+        flow, mask = flow.detach().contiguous(), conv._nhwc(mask.detach())
+        N, _, h, w = flow.shape
+        out = torch.empty((N, 2, 8 * h, 8 * w), device=flow.device, dtype=torch.float32)
+        check(_lib.lib().dvs_convex_up_fwd(flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, h, w, mask_scale, _lib.stream()),
+              "dvs_convex_up_fwd")
+        ctx.save_for_backward(flow, mask)
+        ctx.mask_scale = mask_scale
+        return out
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("RAFT (BasicEncoder, SepConvGRU, mask head) is not built in this package; SmallRAFT is")
+    @staticmethod
+    def backward(ctx, dout):
+        flow, mask = ctx.saved_tensors
+        N, _, h, w = flow.shape
+        need_flow, need_mask = ctx.needs_input_grad[:2]
+        if not (need_flow or need_mask):
+            return None, None, None
+        dout = dout.contiguous()
+        dflow = ws = dmask = None
+        nbytes = 0
+        if need_flow:                                       # the workspace and the gather kernel serve dflow alone
+            dflow = torch.empty_like(flow)
+            nbytes = int(_lib.lib().dvs_convex_up_workspace(N, h, w))
+            ws = torch.empty(nbytes, device=flow.device, dtype=torch.uint8)
+        if need_mask:
+            dmask = torch.empty((N, h, w, 576), device=flow.device, dtype=torch.float32)
+        p = lambda t: t.data_ptr() if t is not None else None
+        check(_lib.lib().dvs_convex_up_bwd(dout.data_ptr(), flow.data_ptr(), mask.data_ptr(), p(dflow), p(dmask), p(ws), nbytes, N, h, w,
+                                           ctx.mask_scale, _lib.stream()), "dvs_convex_up_bwd")
+        return dflow, dmask.permute(0, 3, 1, 2) if need_mask else None, None
 
 
-class SmallRAFT(nn.Module):
+def upsample_flow(flow, mask, mask_scale=1.0):
+    """RAFT.upsample_flow (raft.py:170-181): the convex combination of the 3x3 neighbourhood of 8 * flow, [N,2,h,w], under
+    softmax(mask_scale * mask) over the nine taps of mask [N,576,h,w] (channels_last memory is read in place); planar [N,2,8h,8w]
+    out.  The reference hands in 0.25 * mask; here the raw mask head output and mask_scale=0.25 save that pass.  Differentiable in
+    flow and mask; both directions repeat bit for bit."""
+    for name, t in (("flow", flow), ("mask", mask)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise DvsError("upsample_flow: %s: GPU tensors only (got %s); this package has no CPU path"
+                           % (name, getattr(t, "device", type(t))))
+        if t.dtype != torch.float32:
+            raise DvsError("upsample_flow: %s: fp32 only, got %s" % (name, t.dtype))
+    if flow.dim() != 4 or flow.shape[1] != 2 or min(flow.shape) < 1:
+        raise DvsError("upsample_flow: flow: [N,2,h,w] expected, got %s" % (tuple(flow.shape),))
+    N, _, h, w = flow.shape
+    if tuple(mask.shape) != (N, 576, h, w) or mask.device != flow.device:
+        raise DvsError("upsample_flow: mask must be [%d,576,%d,%d] on %s, got %s on %s"
+                       % (N, h, w, flow.device, tuple(mask.shape), mask.device))
+    return _ConvexUp.apply(flow, mask, float(mask_scale))
+
+
+class NoRaftArgs(DvsError, NotImplementedError):
+    """RAFT(None): a DvsError like every input error of this package, and a NotImplementedError because that is what the name
+    RAFT raised while the full-size model was not built (the precedent of raft_corr.NoCpuPath)."""
+
+
+class _RaftBase(nn.Module):
+    """What SmallRAFT and RAFT share: the input checks."""
+
+    def _check(self, image1, image2, iters, flow_init):
+        who = type(self).__name__
+        for name, t in (("image1", image1), ("image2", image2)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise DvsError("%s: %s: GPU tensors only (got %s); this package has no CPU path"
+                               % (who, name, getattr(t, "device", type(t))))
+            if t.dtype != torch.float32:
+                raise DvsError("%s: %s: fp32 only, got %s" % (who, name, t.dtype))
+            if t.dim() != 4 or t.shape[1] != 3:
+                raise DvsError("%s: %s: [B,3,H,W] expected, got %s" % (who, name, tuple(t.shape)))
+        if image1.shape != image2.shape or image1.device != image2.device:
+            raise DvsError("%s: image1 %s on %s, image2 %s on %s"
+                           % (who, tuple(image1.shape), image1.device, tuple(image2.shape), image2.device))
+        B, _, H, W = image1.shape
+        if H % 8 or W % 8 or H < 128 or W < 128:
+            raise DvsError("%s: images must be multiples of 8 and at least 128x128 (the 4-level correlation pyramid needs "
+                           "16x16 features), got %dx%d" % (who, H, W))
+        if int(iters) < 1:
+            raise DvsError("%s: iters=%r must be at least 1" % (who, iters))
+        if flow_init is not None:
+            if (not torch.is_tensor(flow_init) or flow_init.device != image1.device or flow_init.dtype != torch.float32
+                    or tuple(flow_init.shape) != (B, 2, H // 8, W // 8)):
+                raise DvsError("%s: flow_init must be a fp32 [%d,2,%d,%d] tensor on %s" % (who, B, H // 8, W // 8, image1.device))
+
+
+class RAFT(_RaftBase):
+    """The full-size model (raft.py:122-244): BasicEncoder('instance') and BasicEncoder('batch'), the radius-4 correlation block,
+    BasicUpdateBlock and the convex upsampling (csrc/convexup.hip).
+
+        raft = RAFT({"small": False}); raft.load_state_dict(torch.load("raft-things.pth")); raft = raft.cuda().eval()
+        flow_low, flow_up = raft(image1, image2, iters=20, test_mode=True)      # images in 0 .. 1
+        flows = raft(image1, image2, iters=12)                                  # every iteration's flow, upsampled in one launch
+
+    `args` is a namespace or a dict (small, alternate_corr, mixed_precision, dropout).  test_mode and last_only (an extension) run
+    the mask head and the upsampling at the last iteration only.  GPU and fp32 only."""
+
+    def __init__(self, args):
+        if args is None:
+            raise NoRaftArgs("RAFT: args are required (a namespace or a dict: small=False, alternate_corr, ...), as the reference "
+                             "requires them; RAFT({'small': False}) builds the full-size model")
+        if _option(args, "small", False):
+            raise DvsError("RAFT: small=True is SmallRAFT in this package: use raft.SmallRAFT(args)")
+        if _option(args, "mixed_precision", False):
+            raise DvsError("RAFT: mixed_precision=True is not built: the kernels are fp32; use _lib.set_precision('bf16') for bf16 "
+                           "matrix-core convolutions")
+        dropout = _option(args, "dropout", 0) or 0
+        if dropout > 0:
+            raise DvsError("RAFT: dropout=%r is not built: use dropout=0 (the released checkpoints were trained without)" % (dropout,))
+        super().__init__()
+        self.args = args
+        self.hidden_dim, self.context_dim = 128, 128
+        self.corr_levels, self.corr_radius = 4, 4
+        self.alternate_corr = bool(_option(args, "alternate_corr", False))
+        self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=0.0)
+        self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch", dropout=0.0)
+        self.update_block = BasicUpdateBlock(hidden_dim=self.hidden_dim, corr_levels=self.corr_levels, corr_radius=self.corr_radius)
+
+    def freeze_bn(self):
+        """raft.py:156-159: every BatchNorm2d (the context encoder's) uses its running statistics from here on."""
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+
+    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
+        self._check(image1, image2, iters, flow_init)
+        iters = int(iters)
+        image1 = 2 * image1 - 1.0
+        image2 = 2 * image2 - 1.0
+        hdim, cdim = self.hidden_dim, self.context_dim
+        fmap1, fmap2 = self.fnet([image1, image2])
+        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
+        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
+        cnet = self.cnet(image1)
+        net, inp = torch.split(cnet, [hdim, cdim], dim=1)
+        net = conv._nhwc(torch.tanh(net))
+        inp = conv._nhwc(torch.relu(inp))                   # made once: the update block's hoisted terms are keyed on this object
+        B, _, H, W = image1.shape
+        coords0 = coords_grid(B, H // 8, W // 8, image1.device)
+        coords1 = coords0
+        if flow_init is not None:
+            coords1 = coords1 + flow_init
+        only_last = bool(test_mode or last_only)
+        flows, masks = [], []
+        for it in range(iters):
+            coords1 = coords1.detach()
+            corr = corr_fn(coords1, memory_format=CL)
+            flow = coords1 - coords0
+            want_mask = bool(upsample) and (not only_last or it == iters - 1)
+            net, mask, delta_flow = self.update_block(net, inp, corr, flow, upsample=want_mask)
+            coords1 = coords1 + delta_flow
+            flows.append(coords1 - coords0)
+            masks.append(mask)
+        self.flow_low = [f.detach() for f in flows]         # the 1/8-resolution flows of the last call
+        scale = self.update_block.MASK_SCALE
+        if not upsample:                                    # the block's upsample=False: no mask, bilinear upflow8 as raft.py:234-235
+            up = [upflow8(flows[-1])] if only_last else list(torch.split(upflow8(torch.cat(flows, 0)), B, dim=0))
+        elif only_last:
+            up = [upsample_flow(flows[-1], masks[-1], scale)]
+        else:
+            up = list(torch.split(upsample_flow(torch.cat(flows, 0), torch.cat(masks, 0), scale), B, dim=0))
+        if test_mode:
+            return flows[-1], up[-1]
+        return up
+
+
+class SmallRAFT(_RaftBase):
     def __init__(self, args=None):
         super().__init__()
         self.args = args if args is not None else SimpleNamespace()
@@ -101,29 +262,6 @@ class SmallRAFT(nn.Module):
 
     def freeze_bn(self):
         """raft.py:38-41; there is no BatchNorm in SmallRAFT."""
-
-    def _check(self, image1, image2, iters, flow_init):
-        for name, t in (("image1", image1), ("image2", image2)):
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DvsError("SmallRAFT: %s: GPU tensors only (got %s); this package has no CPU path"
-                               % (name, getattr(t, "device", type(t))))
-            if t.dtype != torch.float32:
-                raise DvsError("SmallRAFT: %s: fp32 only, got %s" % (name, t.dtype))
-            if t.dim() != 4 or t.shape[1] != 3:
-                raise DvsError("SmallRAFT: %s: [B,3,H,W] expected, got %s" % (name, tuple(t.shape)))
-        if image1.shape != image2.shape or image1.device != image2.device:
-            raise DvsError("SmallRAFT: image1 %s on %s, image2 %s on %s"
-                           % (tuple(image1.shape), image1.device, tuple(image2.shape), image2.device))
-        B, _, H, W = image1.shape
-        if H % 8 or W % 8 or H < 128 or W < 128:
-            raise DvsError("SmallRAFT: images must be multiples of 8 and at least 128x128 (the 4-level correlation pyramid needs "
-                           "16x16 features), got %dx%d" % (H, W))
-        if int(iters) < 1:
-            raise DvsError("SmallRAFT: iters=%r must be at least 1" % (iters,))
-        if flow_init is not None:
-            if (not torch.is_tensor(flow_init) or flow_init.device != image1.device or flow_init.dtype != torch.float32
-                    or tuple(flow_init.shape) != (B, 2, H // 8, W // 8)):
-                raise DvsError("SmallRAFT: flow_init must be a fp32 [%d,2,%d,%d] tensor on %s" % (B, H // 8, W // 8, image1.device))
 
     def forward(self, image1, image2, iters=12, flow_init=None, last_only=False):
         self._check(image1, image2, iters, flow_init)

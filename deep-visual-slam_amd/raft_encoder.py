@@ -16,6 +16,9 @@ the tail kernel (norm=False).  Parameter names and shapes are the reference's (c
 layer{2,3}.0.downsample.0, conv2; the norms have no parameters), so the fnet. / cnet. parts of raft-small.pth load with
 load_state_dict.  conv1 reads 3 channels: the image and the filter are zero-padded to 4, as raft_update pads the flow.
 GPU and fp32 only; no host synchronisation in forward or backward.
+
+BasicEncoder (extractor.py:118-192, full-size RAFT's fnet and cnet) follows further down: ResidualBlock stacks with the same
+tail kernel, and norm_fn='batch' on the BatchNorm kernels of bn.py.
 """
 import weakref
 
@@ -24,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, conv, nn_ops
+from . import bn as _bn_ops
 from ._lib import DvsError, check
 from .raft_update import _drop_on_gradient
 
@@ -213,3 +217,195 @@ class SmallEncoder(nn.Module):
         if is_list:
             return torch.split(x, [batch_dim, batch_dim], dim=0)
         return x
+
+
+# ---- the full-size encoder -----------------------------------------------------------------------------------------------------
+BN_WIDTH = {64: 64, 96: 128, 128: 128}      # channels a stage runs at: dvs_bn_* cover C/4 dividing 256, which 96 / 4 = 24 does not
+
+
+class _Residual(nn.Module):
+    """Holds the parameters and buffers of one ResidualBlock (extractor.py:6-56) under the reference's names, in its order."""
+
+    def __init__(self, in_planes, planes, norm_fn, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_planes, planes, kernel_size=3, padding=1, stride=stride)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, padding=1)
+        make = (lambda: nn.BatchNorm2d(planes)) if norm_fn == "batch" else (lambda: nn.Sequential())
+        self.norm1, self.norm2 = make(), make()
+        if stride != 1:
+            self.norm3 = make()
+        self.stride = stride
+        # the reference's Sequential(conv, norm3): norm3 is registered twice, its state-dict keys appear under both names
+        self.downsample = None if stride == 1 else nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride), self.norm3)
+
+
+class BasicEncoder(nn.Module):
+    """extractor.py:118-192: conv1 7x7/2 3->64, norm, ReLU, three stages of two ResidualBlocks (64, 96/2, 128/2), conv2 1x1.
+
+    norm_fn 'instance' (RAFT's fnet) and 'none' run as SmallEncoder does.  'batch' (RAFT's cnet) runs on bn.bn_act in train mode
+    (batch statistics from the convolution's epilogue, running statistics and num_batches_tracked updated as nn.BatchNorm2d does)
+    and on bn.affine_act in eval mode and under freeze_bn (running statistics).  The convolutions in front of a BatchNorm have
+    biases here, unlike ResNet's, and the BatchNorm kernels take the convolution's output without one:
+        train   bn(conv + b) = bn(conv), the batch mean absorbs b; running_mean, which does see it, gets momentum * b added.
+                b receives an exactly-zero gradient (torch's is zero up to rounding).
+        eval    bn(conv + b) = conv * scale + (shift + b * scale), differentiable in b.
+    The 96-channel stage runs zero-padded to 128 channels in the 'batch' form: filters, gamma (1), beta (0) and the running
+    statistics are padded by differentiable torch ops, the padded channels stay exactly zero through ReLU, the residual adds and
+    the next stage's zero input filters, and their gradients are dropped by the padding's backward."""
+
+    def __init__(self, output_dim=128, norm_fn="batch", dropout=0.0):
+        super().__init__()
+        if norm_fn not in ("instance", "batch", "none"):
+            raise DvsError("BasicEncoder: norm_fn=%r is not built: RAFT uses 'instance' (fnet) and 'batch' (cnet); 'none' is built too"
+                           % (norm_fn,))
+        if dropout and dropout > 0:
+            raise DvsError("BasicEncoder: dropout=%r is not built: train with dropout=0 (the released RAFT checkpoints do)" % (dropout,))
+        if int(output_dim) <= 0 or int(output_dim) % 4:
+            raise DvsError("BasicEncoder: output_dim=%r must be a positive multiple of 4" % (output_dim,))
+        self.norm_fn = norm_fn
+        self.norm1 = nn.BatchNorm2d(64) if norm_fn == "batch" else nn.Sequential()
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
+        planes = 64
+        for i, (dim, stride) in enumerate(((64, 1), (96, 2), (128, 2)), 1):
+            setattr(self, "layer%d" % i, nn.Sequential(_Residual(planes, dim, norm_fn, stride), _Residual(dim, dim, norm_fn, 1)))
+            planes = dim
+        self.conv2 = nn.Conv2d(128, int(output_dim), kernel_size=1)
+        for m in self.modules():                                        # extractor.py:150-157
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        self._weights = self._context = None
+
+    def _blocks(self):
+        return [b for i in (1, 2, 3) for b in getattr(self, "layer%d" % i)]
+
+    def _convs(self):
+        out = [self.conv1]
+        for b in self._blocks():
+            out += [b.conv1, b.conv2] + ([b.downsample[0]] if b.downsample is not None else [])
+        return out + [self.conv2]
+
+    def _derive(self):
+        """{conv module: (channels_last weight, bias)} under SmallEncoder's stamp rule.  conv1's filter is zero-padded to 4 input
+        channels; in the 'batch' form every 96 becomes 128 (zero filters, zero input channels, zero biases)."""
+        stamp = (torch.is_grad_enabled(), nn_ops.generation()) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
+        if self._weights is not None and self._weights[0] == stamp:
+            return self._weights[1]
+        wide = (lambda c: BN_WIDTH.get(c, c)) if self.norm_fn == "batch" else (lambda c: c)
+        w = {}
+        for m in self._convs():
+            wt, b = m.weight, m.bias
+            co, ci = wt.shape[:2]
+            pad_o = (wide(co) - co) if m is not self.conv2 else 0
+            pad_i = 1 if m is self.conv1 else wide(ci) - ci
+            if pad_o or pad_i:
+                wt = F.pad(wt, (0, 0, 0, 0, 0, pad_i, 0, pad_o))
+            if pad_o:
+                b = F.pad(b, (0, pad_o))
+            w[m] = (wt.contiguous(memory_format=CL), b)
+        self._weights = (stamp, w)
+        if torch.is_grad_enabled():
+            hook = _drop_on_gradient(weakref.ref(self))     # their graph is freed by the backward pass that delivers these gradients
+            for wt, b in w.values():
+                for t in (wt, b):
+                    if t.requires_grad and not t.is_leaf:
+                        t.register_hook(hook)
+        return w
+
+    # ---- conv -> norm -> ReLU, by norm_fn --------------------------------------------------------------------------------------
+    def _bn(self, y_conv, bias, bn, relu):
+        """[relu](bn(conv + bias)) from the bias-free convolution `y_conv` = (x, weight, stride, padding)."""
+        x, weight, stride, padding = y_conv
+        C = weight.shape[0]
+        pad = C - bn.num_features
+        if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+            raise DvsError("BasicEncoder: BatchNorm2d as the reference builds it expected (affine, running statistics, a momentum)")
+        if bn.training:
+            if _lib.deterministic():                        # no atomic statistics epilogue: an ordered reduction pass (nn_ops.conv_bn_act)
+                y = conv.conv2d(x, weight, None, stride=stride, padding=padding)
+                stats = _bn_ops.channel_stats(y.detach())
+            else:
+                y, stats = conv.conv2d(x, weight, None, stride=stride, padding=padding, want_stats=1)
+            view = _TrainBN(bn, pad, bias)
+            out = _bn_ops.bn_act(y, view, stats, relu=relu)
+            view.write_back()
+            return out
+        inv = torch.rsqrt(bn.running_var + bn.eps)
+        scale = bn.weight * inv
+        shift = bn.bias - bn.running_mean * scale
+        if pad:
+            scale, shift = F.pad(scale, (0, pad), value=1.0), F.pad(shift, (0, pad))
+        y = conv.conv2d(x, weight, None, stride=stride, padding=padding)
+        return _bn_ops.affine_act(y, scale, shift + bias * scale, relu=relu)
+
+    def _unit(self, x, w, m, norm, stride=1, padding=0, relu=True):
+        wt, b = w[m]
+        if self.norm_fn == "instance":
+            return instance_norm_act(conv.conv2d(x, wt, b, stride=stride, padding=padding), relu=relu)
+        if self.norm_fn == "batch":
+            return self._bn((x, wt, stride, padding), b, norm, relu)
+        return conv.conv2d(x, wt, b, stride=stride, padding=padding, act="relu" if relu else None)
+
+    def _block(self, b, w, x):
+        s = b.stride
+        y = self._unit(x, w, b.conv1, b.norm1, s, 1)
+        if b.downsample is not None:
+            x = self._unit(x, w, b.downsample[0], b.norm3, s, 0, relu=False)
+        if self.norm_fn == "instance":
+            wt, bias = w[b.conv2]                           # relu(x + relu(norm2(conv2 y))) is the fused tail
+            return instance_norm_act(conv.conv2d(y, wt, bias, padding=1), norm=True, relu=True, residual=x)
+        y = self._unit(y, w, b.conv2, b.norm2, 1, 1)
+        return instance_norm_act(y, norm=False, relu=False, residual=x)      # relu(x + y), extractor.py:56
+
+    def forward(self, x):
+        is_list = isinstance(x, (tuple, list))
+        if is_list:
+            if len(x) != 2:
+                raise DvsError("BasicEncoder: a list input holds two image batches (extractor.py:171-174), got %d" % len(x))
+            for t in x:
+                _check_map("BasicEncoder: input", t)
+            if x[0].shape != x[1].shape:
+                raise DvsError("BasicEncoder: the two batches differ: %s and %s" % (tuple(x[0].shape), tuple(x[1].shape)))
+            batch_dim = x[0].shape[0]
+            x = torch.cat(list(x), 0)
+        _check_map("BasicEncoder: input", x)
+        if x.shape[1] != 3:
+            raise DvsError("BasicEncoder: 3 input channels expected, got %s" % (tuple(x.shape),))
+        if x.shape[2] < 16 or x.shape[3] < 16:
+            raise DvsError("BasicEncoder: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (tuple(x.shape),))
+        for p in self.parameters():
+            if p.device != x.device or p.dtype != torch.float32:
+                raise DvsError("BasicEncoder: parameters on %s / %s, input on %s / fp32; move the module with .to()"
+                               % (p.device, p.dtype, x.device))
+        w = self._derive()
+        x4 = F.pad(x.permute(0, 2, 3, 1), (0, 1)).permute(0, 3, 1, 2)           # NHWC memory, a zero fourth channel
+        x = self._unit(x4, w, self.conv1, self.norm1, 2, 3)
+        for b in self._blocks():
+            x = self._block(b, w, x)
+        x = conv.conv2d(x, *w[self.conv2])
+        if is_list:
+            return torch.split(x, [batch_dim, batch_dim], dim=0)
+        return x
+
+
+class _TrainBN:
+    """A train-mode nn.BatchNorm2d as bn.bn_act sees it behind a convolution whose bias was left out, `pad` channels wider: gamma
+    padded with ones, beta with zeros (differentiable; the convolution's bias rides on beta with factor 0, so that it receives
+    the exactly-zero gradient it has instead of none), running statistics in padded copies.  write_back() returns them to the
+    module's own buffers and adds momentum * bias to running_mean, which, unlike the output, does see the bias."""
+
+    def __init__(self, bn, pad, conv_bias):
+        self.bn, self.n, self.pad = bn, bn.num_features, pad
+        self.conv_bias = conv_bias.detach()[:self.n]
+        self.weight = F.pad(bn.weight, (0, pad), value=1.0)
+        self.bias = F.pad(bn.bias + 0.0 * conv_bias[:self.n], (0, pad))
+        self.running_mean = F.pad(bn.running_mean, (0, pad)) if pad else bn.running_mean
+        self.running_var = F.pad(bn.running_var, (0, pad), value=1.0) if pad else bn.running_var
+        self.momentum, self.eps, self.num_batches_tracked = bn.momentum, bn.eps, bn.num_batches_tracked
+        self.training = self.track_running_stats = self.affine = True
+
+    def write_back(self):
+        with torch.no_grad():
+            if self.pad:
+                self.bn.running_mean.copy_(self.running_mean[:self.n])
+                self.bn.running_var.copy_(self.running_var[:self.n])
+            self.bn.running_mean.add_(self.conv_bias, alpha=float(self.momentum))

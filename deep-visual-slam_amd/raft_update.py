@@ -19,6 +19,10 @@ with every convolution on conv.conv2d / conv.head_conv2d (the route plan picks t
 and the gate arithmetic on four kernels of its own.  Weights are sliced, concatenated and zero-padded by differentiable torch ops
 once per context, so gradients land on the original parameters, whose names and shapes are the reference's: a raft-small.pth
 sub-dictionary loads with load_state_dict.  GPU and fp32 only; no host synchronisation in forward or backward.
+
+BasicUpdateBlock (update.py:114-136) is the same split, twice: SepConvGRU's (1,5) and (5,1) convolutions are 1x1 convolutions
+over shift_stack(x, axis), the five shifted copies of x side by side along the channels (csrc/shiftstack.hip), with the filter
+re-laid by stacked_filter; the gate kernels are the same four.
 """
 import weakref
 
@@ -167,9 +171,98 @@ def _drop_on_gradient(owner_ref):
     return hook
 
 
-class SmallUpdateBlock(nn.Module):
+class _UpdateBlock(nn.Module):
+    """What the two update blocks share: the parameter holders under the reference's names, the stamp rule of the derived
+    operands and the per-context cache of the hoisted terms.  A subclass sets CTX (channels of `inp`) and provides _derive()
+    and _context_terms(inp, w)."""
+    CTX = None
+
+    def _make_groups(self, layout, source):
+        """layout {group: [(name, Cout, Cin, k, padding)]}, k an int or (kh, kw): nn.Conv2d holders with the reference's init, or,
+        with `source`, holders that share the Parameter objects of a block of the reference's shape."""
+        who = type(self).__name__
+        for group, convs in layout.items():
+            holder = nn.Module()
+            for name, co, ci, k, pad in convs:
+                kh, kw = (k, k) if isinstance(k, int) else k
+                if source is None:
+                    layer = nn.Conv2d(ci, co, (kh, kw), padding=pad)        # holds the parameters (and the reference's init) only
+                else:
+                    theirs = getattr(getattr(source, group, None), name, None)
+                    w, b = getattr(theirs, "weight", None), getattr(theirs, "bias", None)
+                    if not isinstance(w, nn.Parameter) or not isinstance(b, nn.Parameter):
+                        raise DvsError("%s.from_module: %s.%s has no weight / bias parameters" % (who, group, name))
+                    if tuple(w.shape) != (co, ci, kh, kw) or tuple(b.shape) != (co,):
+                        raise DvsError("%s.from_module: %s.%s is %s / %s, expected %s / %s"
+                                       % (who, group, name, tuple(w.shape), tuple(b.shape), (co, ci, kh, kw), (co,)))
+                    layer = nn.Module()
+                    layer.weight, layer.bias = w, b
+                setattr(holder, name, layer)
+            setattr(self, group, holder)
+        self._weights = self._context = None
+
+    # ---- what is made once per context ------------------------------------------------------------------------------------
+    def _stamp(self):
+        """conv._p16_stamp's rule over every parameter (dp.FusedAdam writes weights behind torch's back), plus what decides
+        whether the derived tensors are graph nodes."""
+        gen = nn_ops.generation()
+        return (torch.is_grad_enabled(), gen) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
+
+    def _keep(self, stamp, w, tensors):
+        """Serve the derived operands `w` while the stamp holds; `tensors`: the derived tensors themselves."""
+        self._weights, self._context = (stamp, w), None
+        if torch.is_grad_enabled():
+            # their graph is freed by the backward pass that delivers these gradients: never serve them again after it
+            hook = _drop_on_gradient(weakref.ref(self))
+            for t in tensors:
+                if t.requires_grad and not t.is_leaf:
+                    t.register_hook(hook)
+        return w
+
+    def _hoisted(self, inp, w):
+        """The terms that depend on `inp` and the weights alone (self._context_terms): reused while `inp` is the same tensor
+        object with the same version and requires_grad, and the weights (self._derive's stamp, which includes the grad mode) are
+        the same."""
+        ent = self._context
+        key = (inp._version, inp.requires_grad)
+        if ent is not None and ent[0]() is inp and ent[1] == key:
+            return ent[2]
+        c = self._context_terms(inp, w)
+        hook = _drop_on_gradient(weakref.ref(self))
+        for t in (c if isinstance(c, tuple) else (c,)):
+            if t.requires_grad:
+                t.register_hook(hook)
+        self._context = (weakref.ref(inp), key, c)
+        return c
+
+    # ---- input checks -----------------------------------------------------------------------------------------------------
+    def _check(self, net, inp, corr, flow):
+        who = type(self).__name__
+        want = (("net", net, self.hidden_dim), ("inp", inp, self.CTX), ("corr", corr, self.cor_planes), ("flow", flow, 2))
+        for name, t, _ in want:
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise DvsError("%s: %s: GPU tensors only (got %s); this package has no CPU path"
+                               % (who, name, getattr(t, "device", type(t))))
+            if t.dtype != torch.float32:
+                raise DvsError("%s: %s: fp32 only, got %s" % (who, name, t.dtype))
+            if t.dim() != 4:
+                raise DvsError("%s: %s: [B,C,H,W] expected, got %s" % (who, name, tuple(t.shape)))
+        B, _, H, W = net.shape
+        for name, t, ch in want:
+            if tuple(t.shape) != (B, ch, H, W):
+                raise DvsError("%s: %s must be [%d,%d,%d,%d], got %s" % (who, name, B, ch, H, W, tuple(t.shape)))
+            if t.device != net.device:
+                raise DvsError("%s: %s on %s, net on %s" % (who, name, t.device, net.device))
+        for p in self.parameters():
+            if p.device != net.device or p.dtype != torch.float32:
+                raise DvsError("%s: parameters on %s / %s, inputs on %s / fp32; move the block with .to()"
+                               % (who, p.device, p.dtype, net.device))
+
+
+class SmallUpdateBlock(_UpdateBlock):
     """update.py:99-112 with the reference's parameter names: encoder.{convc1,convf1,convf2,conv}, gru.{convz,convr,convq},
     flow_head.{conv1,conv2}, each .weight / .bias."""
+    CTX = CTX_DIM
 
     def __init__(self, hidden_dim=96, corr_levels=4, corr_radius=3):
         super().__init__()
@@ -196,34 +289,9 @@ class SmallUpdateBlock(nn.Module):
                            "of 4 (the reference's settings give 196 and 324)" % planes)
         self.hidden_dim, self.cor_planes = hidden, planes
         gin = hidden + CTX_DIM + MOTION_DIM
-        layout = {"encoder": [(n, co, ci if ci is not None else planes, k) for n, co, ci, k in _ENCODER],
-                  "gru": [(n, hidden, gin, 3) for n in ("convz", "convr", "convq")],
-                  "flow_head": [("conv1", 128, hidden, 3), ("conv2", 2, 128, 3)]}
-        for group, convs in layout.items():
-            holder = nn.Module()
-            for name, co, ci, k in convs:
-                if source is None:
-                    layer = nn.Conv2d(ci, co, k, padding=k // 2)        # holds the parameters (and the reference's init) only
-                else:
-                    theirs = getattr(getattr(source, group, None), name, None)
-                    w, b = getattr(theirs, "weight", None), getattr(theirs, "bias", None)
-                    if not isinstance(w, nn.Parameter) or not isinstance(b, nn.Parameter):
-                        raise DvsError("SmallUpdateBlock.from_module: %s.%s has no weight / bias parameters" % (group, name))
-                    if tuple(w.shape) != (co, ci, k, k) or tuple(b.shape) != (co,):
-                        raise DvsError("SmallUpdateBlock.from_module: %s.%s is %s / %s, expected %s / %s"
-                                       % (group, name, tuple(w.shape), tuple(b.shape), (co, ci, k, k), (co,)))
-                    layer = nn.Module()
-                    layer.weight, layer.bias = w, b
-                setattr(holder, name, layer)
-            setattr(self, group, holder)
-        self._weights = self._context = None
-
-    # ---- what is made once per context ------------------------------------------------------------------------------------
-    def _stamp(self):
-        """conv._p16_stamp's rule over every parameter (dp.FusedAdam writes weights behind torch's back), plus what decides
-        whether the derived tensors are graph nodes."""
-        gen = nn_ops.generation()
-        return (torch.is_grad_enabled(), gen) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
+        self._make_groups({"encoder": [(n, co, ci if ci is not None else planes, k, k // 2) for n, co, ci, k in _ENCODER],
+                           "gru": [(n, hidden, gin, 3, 1) for n in ("convz", "convr", "convq")],
+                           "flow_head": [("conv1", 128, hidden, 3, 1), ("conv2", 2, 128, 3, 1)]}, source)
 
     def _derive(self):
         """The operands of the launches, from the parameters, by differentiable torch ops."""
@@ -246,54 +314,17 @@ class SmallUpdateBlock(nn.Module):
         w.gx = cl(pad_in(stack[:, hd + CTX_DIM:], 2))                           # motion's 82 channels -> 84
         w.h1 = (cl(f.conv1.weight), f.conv1.bias)
         w.h2 = (cl(f.conv2.weight), f.conv2.bias)
-        self._weights, self._context = (stamp, w), None
-        if torch.is_grad_enabled():
-            # their graph is freed by the backward pass that delivers these gradients: never serve them again after it
-            hook = _drop_on_gradient(weakref.ref(self))
-            for t in (w.c1[0], w.f1[0], w.f2[0], w.m[0], w.gh, w.gq, w.gc[0], w.gc[1], w.gx, w.h1[0], w.h2[0]):
-                if t.requires_grad and not t.is_leaf:
-                    t.register_hook(hook)
-        return w
+        return self._keep(stamp, w, (w.c1[0], w.f1[0], w.f2[0], w.m[0], w.gh, w.gq, w.gc[0], w.gc[1], w.gx, w.h1[0], w.h2[0]))
 
     def _context_conv(self, inp, weight, bias):
         """The hoisted convolution itself (tests count its calls)."""
         return conv.conv2d(inp, weight, bias, padding=1)
 
-    def _hoisted(self, inp, w):
-        """c = conv(inp) + biases of the three gates, [B, 3hd, H, W]: reused while `inp` is the same tensor object with the same
-        version and requires_grad, and the weights (self._derive's stamp, which includes the grad mode) are the same."""
-        ent = self._context
-        key = (inp._version, inp.requires_grad)
-        if ent is not None and ent[0]() is inp and ent[1] == key:
-            return ent[2]
-        c = self._context_conv(inp, *w.gc)
-        if c.requires_grad:
-            c.register_hook(_drop_on_gradient(weakref.ref(self)))
-        self._context = (weakref.ref(inp), key, c)
-        return c
+    def _context_terms(self, inp, w):
+        """c = conv(inp) + biases of the three gates, [B, 3hd, H, W]."""
+        return self._context_conv(inp, *w.gc)
 
     # ---- forward ----------------------------------------------------------------------------------------------------------
-    def _check(self, net, inp, corr, flow):
-        want = (("net", net, self.hidden_dim), ("inp", inp, CTX_DIM), ("corr", corr, self.cor_planes), ("flow", flow, 2))
-        for name, t, _ in want:
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DvsError("SmallUpdateBlock: %s: GPU tensors only (got %s); this package has no CPU path"
-                               % (name, getattr(t, "device", type(t))))
-            if t.dtype != torch.float32:
-                raise DvsError("SmallUpdateBlock: %s: fp32 only, got %s" % (name, t.dtype))
-            if t.dim() != 4:
-                raise DvsError("SmallUpdateBlock: %s: [B,C,H,W] expected, got %s" % (name, tuple(t.shape)))
-        B, _, H, W = net.shape
-        for name, t, ch in want:
-            if tuple(t.shape) != (B, ch, H, W):
-                raise DvsError("SmallUpdateBlock: %s must be [%d,%d,%d,%d], got %s" % (name, B, ch, H, W, tuple(t.shape)))
-            if t.device != net.device:
-                raise DvsError("SmallUpdateBlock: %s on %s, net on %s" % (name, t.device, net.device))
-        for p in self.parameters():
-            if p.device != net.device or p.dtype != torch.float32:
-                raise DvsError("SmallUpdateBlock: parameters on %s / %s, inputs on %s / fp32; move the block with .to()"
-                               % (p.device, p.dtype, net.device))
-
     def forward(self, net, inp, corr, flow):
         self._check(net, inp, corr, flow)
         w = self._derive()
@@ -314,3 +345,167 @@ class SmallUpdateBlock(nn.Module):
         # flow head (update.py:13-14)
         delta_flow = conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
         return net, None, delta_flow
+
+
+# ---- the full-size block -------------------------------------------------------------------------------------------------------
+class _ShiftStack(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, axis):
+        x = conv._nhwc(x.detach())
+        B, Cn, H, W = x.shape
+        out = torch.empty((B, H, W, 5 * Cn), device=x.device, dtype=torch.float32)
+        check(_lib.lib().dvs_shift_stack_fwd(x.data_ptr(), out.data_ptr(), B, H, W, Cn, axis, _lib.stream()), "dvs_shift_stack_fwd")
+        ctx.geometry = (B, Cn, H, W, axis)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, Cn, H, W, axis = ctx.geometry
+        g = conv._nhwc(g)
+        dx = torch.empty((B, H, W, Cn), device=g.device, dtype=torch.float32)
+        check(_lib.lib().dvs_shift_stack_bwd(g.data_ptr(), dx.data_ptr(), B, H, W, Cn, axis, _lib.stream()), "dvs_shift_stack_bwd")
+        return dx.permute(0, 3, 1, 2), None
+
+
+def shift_stack(x, axis):
+    """[B,5C,H,W] (channels_last memory) with channel t*C + c = x[:, c] moved by t - 2 along W (axis 0) or H (axis 1), zeros
+    outside: a (1,5) / (5,1) convolution of x, padding (0,2) / (2,0), is the 1x1 convolution of this tensor with
+    stacked_filter(weight).  fp32 GPU tensors, C % 4 == 0; differentiable."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise DvsError("shift_stack: GPU tensors only (got %s); this package has no CPU path" % (getattr(x, "device", type(x)),))
+    if x.dtype != torch.float32:
+        raise DvsError("shift_stack: fp32 only, got %s" % x.dtype)
+    if x.dim() != 4 or x.shape[1] % 4 or min(x.shape) < 1:
+        raise DvsError("shift_stack: [B,C,H,W] with C %% 4 == 0 expected, got %s" % (tuple(x.shape),))
+    if axis not in (0, 1):
+        raise DvsError("shift_stack: axis=%r must be 0 (taps along W) or 1 (taps along H)" % (axis,))
+    return _ShiftStack.apply(x, int(axis))
+
+
+def stacked_filter(weight):
+    """The [Cout, 5*Cin, 1, 1] filter over shift_stack(x, axis) of a [Cout,Cin,1,5] (axis 0) or [Cout,Cin,5,1] (axis 1) filter:
+    input channel t*Cin + c is tap t of channel c.  A differentiable re-layout."""
+    co, ci, kh, kw = weight.shape
+    if (kh, kw) == (1, 5):
+        return weight.permute(0, 3, 2, 1).reshape(co, 5 * ci, 1, 1)
+    if (kh, kw) == (5, 1):
+        return weight.permute(0, 2, 3, 1).reshape(co, 5 * ci, 1, 1)
+    raise DvsError("stacked_filter: a (1,5) or (5,1) filter expected, got %s" % (tuple(weight.shape),))
+
+
+def split_gru_filters(wz, wr, wq, bz, br, bq, hidden, ctx):
+    """The SepConvGRU pass's three filters over cat[h(hidden), inp(ctx), motion] cut by input block and stacked by gate, each as
+    the stacked 1x1 filter: (gh [2hd] on stack(h), gq [hd] on stack(r*h), gc [3hd] on stack(inp), bias [3hd], gx [3hd] on
+    stack(motion))."""
+    stack = torch.cat([wz, wr, wq], 0)
+    cut = lambda t: stacked_filter(t).contiguous(memory_format=CL)
+    return (cut(stack[:2 * hidden, :hidden]), cut(stack[2 * hidden:, :hidden]), cut(stack[:, hidden:hidden + ctx]),
+            torch.cat([bz, br, bq]), cut(stack[:, hidden + ctx:]))
+
+
+class _BasicWeights:
+    """The kernels' view of BasicUpdateBlock's parameters; gru[axis] = split_gru_filters of that pass."""
+    __slots__ = ("c1", "c2", "f1", "f2", "m", "gru", "h1", "h2", "m1", "m2")
+
+
+class BasicUpdateBlock(_UpdateBlock):
+    """update.py:114-136 with the reference's parameter names: encoder.{convc1,convc2,convf1,convf2,conv},
+    gru.{convz1,convr1,convq1,convz2,convr2,convq2}, flow_head.{conv1,conv2}, mask.{0,2}, each .weight / .bias.
+
+    SepConvGRU is the split of the module docstring, twice: a horizontal pass whose (1,5) filters act on shift_stack(., 0) and a
+    vertical pass whose (5,1) filters act on shift_stack(., 1), every contraction a 1x1 convolution with K = 5 * 128 on
+    conv.conv2d.  Both passes' context terms are hoisted.  forward returns (net, mask, delta_flow); mask is the RAW output of the
+    mask head, [B,576,H,W] in channels_last memory: the reference's 0.25 is raft.upsample_flow's mask_scale."""
+    CTX = 128
+    MASK_SCALE = 0.25       # update.py:135
+
+    def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4):
+        super().__init__()
+        self._setup(int(hidden_dim), int(corr_levels) * (2 * int(corr_radius) + 1) ** 2, None)
+
+    @classmethod
+    def from_module(cls, block):
+        """Wrap a block of the reference's shape (.encoder / .gru / .flow_head / .mask), sharing its Parameter objects."""
+        try:
+            hidden, planes = block.gru.convz1.weight.shape[0], block.encoder.convc1.weight.shape[1]
+        except AttributeError as e:
+            raise DvsError("BasicUpdateBlock.from_module: not a BasicUpdateBlock (%s)" % e)
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._setup(int(hidden), int(planes), block)
+        return self
+
+    def _setup(self, hidden, planes, source):
+        if hidden != 128:
+            raise DvsError("BasicUpdateBlock: hidden_dim=%d: the motion encoder's 128 channels and FlowHead(128, 256) fix it at 128 "
+                           "(raft.py:134)" % hidden)
+        if planes <= 0 or planes % 4:
+            raise DvsError("BasicUpdateBlock: corr_levels * (2 * corr_radius + 1)^2 = %d correlation planes must be a multiple "
+                           "of 4 (the reference's settings give 196 and 324)" % planes)
+        self.hidden_dim, self.cor_planes = hidden, planes
+        gin = hidden + self.CTX + 128
+        self._make_groups({
+            "encoder": [("convc1", 256, planes, 1, 0), ("convc2", 192, 256, 3, 1), ("convf1", 128, 2, 7, 3), ("convf2", 64, 128, 3, 1),
+                        ("conv", 126, 256, 3, 1)],
+            "gru": [(n + "1", hidden, gin, (1, 5), (0, 2)) for n in ("convz", "convr", "convq")]
+                   + [(n + "2", hidden, gin, (5, 1), (2, 0)) for n in ("convz", "convr", "convq")],
+            "flow_head": [("conv1", 256, hidden, 3, 1), ("conv2", 2, 256, 3, 1)],
+            "mask": [("0", 256, 128, 3, 1), ("2", 576, 256, 1, 0)]}, source)
+
+    def _derive(self):
+        stamp = self._stamp()
+        if self._weights is not None and self._weights[0] == stamp:
+            return self._weights[1]
+        hd = self.hidden_dim
+        e, g, f = self.encoder, self.gru, self.flow_head
+        m0, m2 = getattr(self.mask, "0"), getattr(self.mask, "2")
+        cl = lambda t: t.contiguous(memory_format=CL)
+        w = _BasicWeights()
+        w.c1 = (cl(e.convc1.weight), e.convc1.bias)
+        w.c2 = (cl(e.convc2.weight), e.convc2.bias)
+        w.f1 = (cl(F.pad(e.convf1.weight, (0, 0, 0, 0, 0, 2))), e.convf1.bias)   # flow's 2 channels -> 4
+        w.f2 = (cl(e.convf2.weight), e.convf2.bias)
+        # 126 outputs -> 128: two zero filters (and zero biases) whose relu(0) = 0 channels make room for the flow
+        w.m = (cl(F.pad(e.conv.weight, (0, 0, 0, 0, 0, 0, 0, 2))), F.pad(e.conv.bias, (0, 2)))
+        w.gru = tuple(split_gru_filters(*(getattr(g, n + s).weight for n in ("convz", "convr", "convq")),
+                                        *(getattr(g, n + s).bias for n in ("convz", "convr", "convq")), hd, self.CTX)
+                      for s in ("1", "2"))
+        w.h1 = (cl(f.conv1.weight), f.conv1.bias)
+        w.h2 = (cl(f.conv2.weight), f.conv2.bias)
+        w.m1 = (cl(m0.weight), m0.bias)
+        w.m2 = (cl(m2.weight), m2.bias)
+        return self._keep(stamp, w, (w.c1[0], w.c2[0], w.f1[0], w.f2[0], w.m[0], w.m[1], w.h1[0], w.h2[0], w.m1[0], w.m2[0])
+                          + w.gru[0] + w.gru[1])
+
+    def _context_conv(self, stacked_inp, weight, bias):
+        """One pass's hoisted convolution itself (tests count its calls)."""
+        return conv.conv2d(stacked_inp, weight, bias)
+
+    def _context_terms(self, inp, w):
+        """(c of the horizontal pass, c of the vertical pass), each conv(stack(inp)) + the three biases, [B, 3hd, H, W]."""
+        return tuple(self._context_conv(shift_stack(inp, axis), w.gru[axis][2], w.gru[axis][3]) for axis in (0, 1))
+
+    def forward(self, net, inp, corr, flow, upsample=True):
+        self._check(net, inp, corr, flow)
+        w = self._derive()
+        c = self._hoisted(inp, w)
+        net = conv._nhwc(net)
+        # motion encoder (update.py:89-97); flow as the 4-channel NHWC tensor of SmallUpdateBlock
+        flow4 = F.pad(flow.permute(0, 2, 3, 1), (0, 2)).contiguous().permute(0, 3, 1, 2)
+        cor = conv.conv2d(corr, *w.c1, act="relu")
+        cor = conv.conv2d(cor, *w.c2, padding=1, act="relu")
+        flo = conv.conv2d(flow4, *w.f1, padding=3, act="relu")
+        flo = conv.conv2d(flo, *w.f2, padding=1, act="relu")
+        out = conv.conv2d(torch.cat([cor, flo], 1), *w.m, padding=1, act="relu")     # 128 channels, the last two zero
+        motion = torch.cat([out[:, :126], flow4[:, :2]], 1)                           # the flow takes their place
+        # SepConvGRU (update.py:45-60): horizontal, then vertical
+        for axis in (0, 1):
+            gh, gq, _, _, gx = w.gru[axis]
+            a_x = conv.conv2d(shift_stack(motion, axis), gx, None)
+            a_h = conv.conv2d(shift_stack(net, axis), gh, None)
+            net = conv_gru(a_h, a_x, c[axis], net, lambda rh: conv.conv2d(shift_stack(rh, axis), gq, None))
+        delta_flow = conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
+        mask = None
+        if upsample:
+            mask = conv.conv2d(conv.conv2d(net, *w.m1, padding=1, act="relu"), *w.m2)
+        return net, mask, delta_flow

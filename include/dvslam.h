@@ -789,6 +789,49 @@ int dvs_pool_fc_fwd(const float* y, const float* W, const float* b, float* out, 
 int dvs_pool_fc_bwd(const float* dout, const float* y, const float* mean, const float* W, float* dy, float* dW, float* db, int N,
                     long long P, int C, int J, int relu, float scale, void* stream);   /* autograd of model/posenet_single.py:137-142 */
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Convex 8x flow upsampling
+ *     replaces RAFT.upsample_flow, model/raft/core/raft.py:170-181 (view, softmax, F.unfold, mul, sum, permute, reshape) and the
+ *     `.25 *` of BasicUpdateBlock.forward, model/raft/core/update.py:135
+ *
+ *   flow [N][2][h][w] planar; mask [N][h][w][576] NHWC, channel k*64 + i*8 + j with tap k = ky*3 + kx; out [N][2][8h][8w] planar.
+ *       p_k                    = softmax_k(mask_scale * mask[n][y][x][k*64 + i*8 + j])          the maximum subtracted first
+ *       out[n][ch][8y+i][8x+j] = sum_k p_k * 8 * flow[n][ch][y+ky-1][x+kx-1]                    0 outside the map
+ *   dvs_convex_up_bwd: for dout = dL/dout, with the softmax recomputed from the mask and t_k = sum_ch dout_ch * 8 * flow_ch(tap k):
+ *       dmask[k]               = mask_scale * p_k * (t_k - sum_k' p_k' t_k')                    [N][h][w][576], overwritten
+ *       s[n][y][x][k][ch]      = sum_ij p_k * dout_ch                                           the workspace
+ *       dflow[n][ch][y'][x']   = 8 * sum_k s[n][y'-ky+1][x'-kx+1][k][ch]                        in-range neighbours, ascending k
+ *   expf of the HIP math library on fp32 values; the nine-term sums and the normalisation are carried in fp64 registers and
+ *   rounded to fp32 once, so a one-hot softmax returns 8 * flow of its tap exactly and a constant flow its constant.
+ *   The mask is read once per direction.  No atomics, a fixed order: both directions are bit-reproducible.  64-bit element offsets.
+ *   workspace: dvs_convex_up_workspace(N, h, w) = N*h*w*18*4 bytes (0 for invalid arguments), device memory, backward only.
+ *   dflow or dmask (not both) may be NULL: that gradient is not computed; the workspace is needed, and read, with dflow only.
+ *   1 <= N <= 65535, h, w >= 1, 64 * h * w < 2^31, finite mask_scale; 16-byte aligned pointers.  DVS_ERR_INVALID, before any
+ *   launch, for a null or misaligned pointer, a shape out of range, a workspace that is too small.
+ *   dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+size_t dvs_convex_up_workspace(int N, int h, int w);
+int dvs_convex_up_fwd(const float* flow, const float* mask, float* out, int N, int h, int w, float mask_scale, void* stream);
+int dvs_convex_up_bwd(const float* dout, const float* flow, const float* mask, float* dflow, float* dmask, void* workspace,
+                      size_t workspace_bytes, int N, int h, int w, float mask_scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Shift-stack: the five taps of a (1,5) / (5,1) convolution along the channels
+ *     lets SepConvGRU's convolutions, model/raft/core/update.py:36-42, run as 1x1 convolutions with K = 5 * Cin
+ *
+ *   x [N][H][W][C] NHWC, C % 4 == 0; (dy, dx) = (0, 1) for axis 0 (taps along W), (1, 0) for axis 1 (taps along H).
+ *       x5[n][y][x][t*C + c] = x[n][y + dy*(t-2)][x + dx*(t-2)][c]   for t = 0 .. 4, 0 outside the map          [N][H][W][5C]
+ *   dvs_shift_stack_bwd, the adjoint:
+ *       dx[n][y][x][c] = sum_t dx5[n][y - dy*(t-2)][x - dx*(t-2)][t*C + c]   over the in-range sources, in ascending t
+ *   A (1,5) convolution with padding (0,2) and filter Wt [Cout][Cin][1][5] is the 1x1 convolution of x5 (axis 0) with
+ *   Wt.permute(0,3,2,1).reshape(Cout, 5*Cin, 1, 1); a (5,1) one likewise with axis 1 and the H tap.
+ *   One lane moves 16 bytes; no atomics, every element written once: bit-reproducible.  64-bit element offsets.
+ *   DVS_ERR_INVALID, before any launch, for a null or misaligned pointer, N, H, W < 1, C <= 0, C % 4 != 0, axis not 0 or 1.
+ *   dvs_set_precision does not affect these kernels.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_shift_stack_fwd(const float* x, float* x5, int N, int H, int W, int C, int axis, void* stream);
+int dvs_shift_stack_bwd(const float* dx5, float* dx, int N, int H, int W, int C, int axis, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
