@@ -191,6 +191,9 @@ _SIGNATURES = {
     "dvs_convex_up_bwd": (C.c_int, [_vp] * 6 + [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
     "dvs_shift_stack_fwd": (C.c_int, [_vp, _vp] + [C.c_int] * 5 + [_vp]),
     "dvs_shift_stack_bwd": (C.c_int, [_vp, _vp] + [C.c_int] * 5 + [_vp]),
+    "dvs_forward_interp": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "dvs_flow_radmax": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),
+    "dvs_flow_to_image": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp]),
 }
 
 _lib = None

@@ -832,6 +832,63 @@ int dvs_convex_up_bwd(const float* dout, const float* flow, const float* mask, f
 int dvs_shift_stack_fwd(const float* x, float* x5, int N, int H, int W, int C, int axis, void* stream);
 int dvs_shift_stack_bwd(const float* dx5, float* dx, int N, int H, int W, int C, int axis, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Warm start: the previous pair's low-resolution flow pushed forward
+ *     replaces forward_interpolate, model/raft/core/utils/utils.py:26-54 (a host copy and two scipy griddata(method='nearest') calls)
+ *
+ *   flow, out [N][2][h][w] fp32 planar, channel 0 = dx, 1 = dy; P = h * w.  Per image, with (xj, yj) the integer grid:
+ *       x1[j] = xj + dx[j],  y1[j] = yj + dy[j]                  in fp64 (int64 grid + fp32 flow, as NumPy promotes them)
+ *       valid[j]  iff  0 < x1[j] < w  and  0 < y1[j] < h          strictly; a NaN or infinite flow is never valid
+ *       d2(i, j)  = (x1[j] - xi)^2 + (y1[j] - yi)^2               fp64, each operation rounded on its own
+ *       out[:, i] = flow[:, j*],  j* = the valid j with the smallest d2(i, j), the LOWEST j among equal d2
+ *   The reference's KD-tree defines no answer at an exact tie; the lowest row-major source index is this package's definition.
+ *   An image without a valid source returns zeros.  The reference has no flow to give there (griddata on zero points returns NaN
+ *   under SciPy 1.15); zeros, a cold start, are this package's extension.
+ *   A brute-force search, P * P distances per image: a workgroup owns 64 grid pixels, its 16 waves share each tile of 1024 sources
+ *   staged in LDS and their answers are merged by the same (d2, j) order, so no split or tile size can change a bit of the result.
+ *   No atomics, no workspace; an image's result does not depend on the other images of the batch.
+ *   1 <= N <= 65535, h, w >= 1, 1 <= P <= 65536 (the measured time at the cap: DESIGN.md section 21);
+ *   4-byte aligned pointers (one image of a batch is a valid argument); out must not overlap flow.  DVS_ERR_INVALID, before any
+ *   launch, otherwise.
+ *   dvs_set_precision does not affect this entry.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_forward_interp(const float* flow, float* out, int N, int h, int w, void* stream);   /* utils/utils.py:26-54 */
+
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Flow colouring
+ *     replaces flow_to_image and flow_uv_to_colors, model/raft/core/utils/flow_viz.py:109-132 and 70-106, as called from
+ *     model/raft/raft.py:26-68 (a host copy of the full-resolution flow and a NumPy pass)
+ *
+ *   flow: fp32, u of pixel (n, y, x) at flow[n * 2 * plane_stride + y * row_stride + x] and v one plane_stride further (element
+ *   strides), so the un-padded view of a padded [N][2][Hp][Wp] flow is read in place: plane_stride = Hp * Wp, row_stride = Wp.
+ *   radmax [N] fp32; out [N][H][W][3] uint8, dense.  clip_flow < 0: no clipping.  Per image, the reference's arithmetic ladder under
+ *   NumPy >= 2 scalar promotion (a Python float beside a float32 array stays float32):
+ *     fp32, every operation rounded on its own (no contraction), division and square root correctly rounded:
+ *       u, v     = clip(u, 0, clip_flow), clip(v, 0, clip_flow)          the lower bound IS 0, as in flow_viz.py:124
+ *       radmax   = max over the image of sqrt(u*u + v*v)                 dvs_flow_radmax; a NaN wins, as in np.max
+ *       den      = radmax + 1e-5f;  u = u / den;  v = v / den;  rad = sqrt(u*u + v*v)
+ *       a        = atan2f(-v, -u) / 3.14159274f;  fk = (a + 1) / 2 * 54
+ *     fp64:
+ *       k0 = floor(fk);  k1 = k0 + 1, 55 -> 0;  f = fk - k0;  c = wheel / 255.0
+ *       col      = (1 - f) * c[k0] + f * c[k1];   col = rad <= 1 ? 1 - rad * (1 - col) : 0.75 * col;   byte = floor(255 * col)
+ *   bgr = 1 stores the channels in reverse.  atan2f is the HIP math library's: the one operation of the ladder that is correctly
+ *   rounded on neither side, so a byte whose value sits on a floor() boundary may differ by one from NumPy's (tests/test_flowstage_gpu.py
+ *   states the rule).  The 55 x 3 wheel is computed from the six segment lengths 15, 6, 4, 11, 13, 6; k0 is clamped to 0 .. 54 before
+ *   it indexes the table and the byte to 0 .. 255, so no input value (NaN, infinity) can read or write outside.
+ *   dvs_flow_radmax: one hipMemsetAsync and one launch; the only atomic is an INTEGER atomicMax on the bit pattern of a
+ *   non-negative fp32, and a maximum is exact in any order: the result does not depend on the launch geometry.
+ *   dvs_flow_to_image: reads radmax from device memory (no host synchronisation between the two calls); 8 bytes read and 3 written
+ *   per pixel; a lane stores four pixels as three dwords, and reads them as two float4 where W, both strides and the pointer are
+ *   multiples of 4 elements / 16 bytes.
+ *   1 <= N <= 65535, H, W >= 1, N * H * W < 2^31, row_stride >= W, plane_stride >= (H - 1) * row_stride + W, clip_flow not NaN,
+ *   bgr 0 or 1; flow and radmax 4-byte, out 16-byte aligned.  DVS_ERR_INVALID, before any launch or memset, otherwise.
+ *   dvs_set_precision does not affect these entries.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_flow_radmax(const float* flow, long long plane_stride, long long row_stride, int N, int H, int W, float clip_flow,
+                    float* radmax, void* stream);                                           /* utils/flow_viz.py:123-128 */
+int dvs_flow_to_image(const float* flow, long long plane_stride, long long row_stride, const float* radmax, unsigned char* out, int N,
+                      int H, int W, float clip_flow, int bgr, void* stream);              /* utils/flow_viz.py:70-106, 129-132 */
+
 #ifdef __cplusplus
 }
 #endif
