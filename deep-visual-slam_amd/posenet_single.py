@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from . import _lib, nn_ops
 from . import conv as _conv
 from ._lib import DvsError, check
+from ._raft_host import gpu_arg
 from .raft import SmallRAFT
 from .resnet_encoder import ResnetEncoder
 
@@ -121,10 +122,7 @@ def pool_fc(y, weight, bias=None, relu=True, scale=1.0):
     """scale * (mean over H x W of relu(y)) @ weight.T + scale * bias of a [N,C,H,W] fp32 GPU tensor: [N,J].  Differentiable in y,
     weight and bias; bit-reproducible in both directions."""
     for name, t in (("y", y), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise DvsError("pool_fc: %s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
-        if t.dtype != torch.float32:
-            raise DvsError("pool_fc: %s: fp32 only, got %s" % (name, t.dtype))
+        gpu_arg("pool_fc: " + name, t)
     if y.dim() != 4 or weight.dim() != 2 or weight.shape[1] != y.shape[1] or (bias is not None and tuple(bias.shape) != (weight.shape[0],)):
         raise DvsError("pool_fc: y [N,C,H,W], weight [J,C], bias [J] expected, got %s, %s, %s"
                        % (tuple(y.shape), tuple(weight.shape), tuple(bias.shape) if bias is not None else None))
@@ -164,12 +162,8 @@ class FlowPoseNet(nn.Module):
         self.pose_cnn.to(memory_format=torch.channels_last)     # weights as [Cout][kh][kw][Cin], as everywhere in the package
 
     def _check(self, x):
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise DvsError("FlowPoseNet: GPU tensors only (got %s); this package has no CPU path" % (getattr(x, "device", type(x)),))
-        if x.dtype != torch.float32:
-            raise DvsError("FlowPoseNet: fp32 only, got %s" % x.dtype)
-        if x.dim() != 4 or x.shape[1] != 6 or x.shape[0] < 1:
-            raise DvsError("FlowPoseNet: [B,6,H,W] expected (two RGB frames along the channels), got %s" % (tuple(x.shape),))
+        gpu_arg("FlowPoseNet", x, "[B,6,H,W] expected (two RGB frames along the channels)",
+                ok=lambda shape: shape[1] == 6 and shape[0] >= 1)
 
     def extract_flow(self, x1, x2):
         return self.flow_net(x1, x2, iters=self.iters, last_only=True)[-1]

@@ -18,11 +18,10 @@ import torch.nn as nn
 
 from . import _lib, conv
 from ._lib import DvsError, check
+from ._raft_host import CL, gpu_arg
 from .raft_corr import AlternateCorrBlock, CorrBlock
 from .raft_encoder import BasicEncoder, SmallEncoder
 from .raft_update import BasicUpdateBlock, SmallUpdateBlock
-
-CL = torch.channels_last
 
 
 def _flow_layout(t):
@@ -32,6 +31,10 @@ def _flow_layout(t):
     if not t.is_contiguous(memory_format=CL):
         t = t.contiguous(memory_format=CL)
     return t, 0
+
+
+def _is_flow(shape):
+    return shape[1] == 2 and min(shape) >= 1
 
 
 class _Upflow8(torch.autograd.Function):
@@ -59,12 +62,7 @@ class _Upflow8(torch.autograd.Function):
 def upflow8(flow):
     """8 * F.interpolate(flow, 8x, mode='bilinear', align_corners=True) of a [N,2,h,w] fp32 GPU tensor in planar or channels_last
     memory (utils/utils.py:80-82); planar [N,2,8h,8w] out.  Differentiable; both directions repeat bit for bit."""
-    if not torch.is_tensor(flow) or not flow.is_cuda:
-        raise DvsError("upflow8: GPU tensors only (got %s); this package has no CPU path" % (getattr(flow, "device", type(flow)),))
-    if flow.dtype != torch.float32:
-        raise DvsError("upflow8: fp32 only, got %s" % flow.dtype)
-    if flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] < 1 or flow.shape[2] < 1 or flow.shape[3] < 1:
-        raise DvsError("upflow8: [N,2,h,w] expected, got %s" % (tuple(flow.shape),))
+    gpu_arg("upflow8", flow, "[N,2,h,w] expected", ok=_is_flow)
     return _Upflow8.apply(flow)
 
 
@@ -121,14 +119,8 @@ def upsample_flow(flow, mask, mask_scale=1.0):
     softmax(mask_scale * mask) over the nine taps of mask [N,576,h,w] (channels_last memory is read in place); planar [N,2,8h,8w]
     out.  The reference hands in 0.25 * mask; here the raw mask head output and mask_scale=0.25 save that pass.  Differentiable in
     flow and mask; both directions repeat bit for bit."""
-    for name, t in (("flow", flow), ("mask", mask)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise DvsError("upsample_flow: %s: GPU tensors only (got %s); this package has no CPU path"
-                           % (name, getattr(t, "device", type(t))))
-        if t.dtype != torch.float32:
-            raise DvsError("upsample_flow: %s: fp32 only, got %s" % (name, t.dtype))
-    if flow.dim() != 4 or flow.shape[1] != 2 or min(flow.shape) < 1:
-        raise DvsError("upsample_flow: flow: [N,2,h,w] expected, got %s" % (tuple(flow.shape),))
+    gpu_arg("upsample_flow: flow", flow, "[N,2,h,w] expected", ok=_is_flow)
+    gpu_arg("upsample_flow: mask", mask)
     N, _, h, w = flow.shape
     if tuple(mask.shape) != (N, 576, h, w) or mask.device != flow.device:
         raise DvsError("upsample_flow: mask must be [%d,576,%d,%d] on %s, got %s on %s"
@@ -142,18 +134,12 @@ class NoRaftArgs(DvsError, NotImplementedError):
 
 
 class _RaftBase(nn.Module):
-    """What SmallRAFT and RAFT share: the input checks."""
+    """What SmallRAFT and RAFT share: the input checks, the forward loop and the one upsampling launch behind it."""
 
     def _check(self, image1, image2, iters, flow_init):
         who = type(self).__name__
         for name, t in (("image1", image1), ("image2", image2)):
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DvsError("%s: %s: GPU tensors only (got %s); this package has no CPU path"
-                               % (who, name, getattr(t, "device", type(t))))
-            if t.dtype != torch.float32:
-                raise DvsError("%s: %s: fp32 only, got %s" % (who, name, t.dtype))
-            if t.dim() != 4 or t.shape[1] != 3:
-                raise DvsError("%s: %s: [B,3,H,W] expected, got %s" % (who, name, tuple(t.shape)))
+            gpu_arg("%s: %s" % (who, name), t, "[B,3,H,W] expected", ok=lambda shape: shape[1] == 3)
         if image1.shape != image2.shape or image1.device != image2.device:
             raise DvsError("%s: image1 %s on %s, image2 %s on %s"
                            % (who, tuple(image1.shape), image1.device, tuple(image2.shape), image2.device))
@@ -167,6 +153,48 @@ class _RaftBase(nn.Module):
             if (not torch.is_tensor(flow_init) or flow_init.device != image1.device or flow_init.dtype != torch.float32
                     or tuple(flow_init.shape) != (B, 2, H // 8, W // 8)):
                 raise DvsError("%s: flow_init must be a fp32 [%d,2,%d,%d] tensor on %s" % (who, B, H // 8, W // 8, image1.device))
+
+    def _iterate(self, image1, image2, iters, flow_init, want_mask=None):
+        """raft.py:76-117 and 183-239 up to the upsampling: (the 1/8-resolution flow of every iteration, the update block's mask
+        of every iteration).  want_mask(it, iters) decides whether iteration `it` runs the block's mask head; None is for a
+        block without one."""
+        self._check(image1, image2, iters, flow_init)
+        iters = int(iters)
+        image1 = 2 * image1 - 1.0
+        image2 = 2 * image2 - 1.0
+        fmap1, fmap2 = self.fnet([image1, image2])
+        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
+        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
+        net, inp = torch.split(self.cnet(image1), [self.hidden_dim, self.context_dim], dim=1)
+        net = conv._nhwc(torch.tanh(net))
+        inp = conv._nhwc(torch.relu(inp))                   # made once: the update block's hoisted terms are keyed on this object
+        B, _, H, W = image1.shape
+        coords0 = coords_grid(B, H // 8, W // 8, image1.device)
+        coords1 = coords0
+        if flow_init is not None:
+            coords1 = coords1 + flow_init
+        flows, masks = [], []
+        for it in range(iters):
+            coords1 = coords1.detach()
+            corr = corr_fn(coords1, memory_format=CL)
+            flow = coords1 - coords0
+            options = {} if want_mask is None else {"upsample": want_mask(it, iters)}
+            net, mask, delta_flow = self.update_block(net, inp, corr, flow, **options)
+            coords1 = coords1 + delta_flow
+            flows.append(coords1 - coords0)
+            masks.append(mask)
+        self.flow_low = [f.detach() for f in flows]         # the 1/8-resolution flows of the last call (RAFT's test_mode output)
+        return flows, masks
+
+    def _upsampled(self, flows, masks, only_last):
+        """The list of full-resolution flows, of the last iteration alone or of all of them by ONE launch (N = iters * B): upflow8
+        (utils/utils.py:80-82) without masks, the update block's convex upsampling with them."""
+        pick = (lambda ts: ts[-1]) if only_last else (lambda ts: torch.cat(ts, 0))
+        if masks is None:
+            up = upflow8(pick(flows))
+        else:
+            up = upsample_flow(pick(flows), pick(masks), self.update_block.MASK_SCALE)
+        return [up] if only_last else list(torch.split(up, flows[0].shape[0], dim=0))
 
 
 class RAFT(_RaftBase):
@@ -208,42 +236,11 @@ class RAFT(_RaftBase):
                 m.eval()
 
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
-        self._check(image1, image2, iters, flow_init)
-        iters = int(iters)
-        image1 = 2 * image1 - 1.0
-        image2 = 2 * image2 - 1.0
-        hdim, cdim = self.hidden_dim, self.context_dim
-        fmap1, fmap2 = self.fnet([image1, image2])
-        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
-        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
-        cnet = self.cnet(image1)
-        net, inp = torch.split(cnet, [hdim, cdim], dim=1)
-        net = conv._nhwc(torch.tanh(net))
-        inp = conv._nhwc(torch.relu(inp))                   # made once: the update block's hoisted terms are keyed on this object
-        B, _, H, W = image1.shape
-        coords0 = coords_grid(B, H // 8, W // 8, image1.device)
-        coords1 = coords0
-        if flow_init is not None:
-            coords1 = coords1 + flow_init
         only_last = bool(test_mode or last_only)
-        flows, masks = [], []
-        for it in range(iters):
-            coords1 = coords1.detach()
-            corr = corr_fn(coords1, memory_format=CL)
-            flow = coords1 - coords0
-            want_mask = bool(upsample) and (not only_last or it == iters - 1)
-            net, mask, delta_flow = self.update_block(net, inp, corr, flow, upsample=want_mask)
-            coords1 = coords1 + delta_flow
-            flows.append(coords1 - coords0)
-            masks.append(mask)
-        self.flow_low = [f.detach() for f in flows]         # the 1/8-resolution flows of the last call
-        scale = self.update_block.MASK_SCALE
-        if not upsample:                                    # the block's upsample=False: no mask, bilinear upflow8 as raft.py:234-235
-            up = [upflow8(flows[-1])] if only_last else list(torch.split(upflow8(torch.cat(flows, 0)), B, dim=0))
-        elif only_last:
-            up = [upsample_flow(flows[-1], masks[-1], scale)]
-        else:
-            up = list(torch.split(upsample_flow(torch.cat(flows, 0), torch.cat(masks, 0), scale), B, dim=0))
+        flows, masks = self._iterate(image1, image2, iters, flow_init,
+                                     lambda it, n: bool(upsample) and (not only_last or it == n - 1))
+        # upsample=False is the block's: no mask, bilinear upflow8 as raft.py:234-235
+        up = self._upsampled(flows, masks if upsample else None, only_last)
         if test_mode:
             return flows[-1], up[-1]
         return up
@@ -264,31 +261,5 @@ class SmallRAFT(_RaftBase):
         """raft.py:38-41; there is no BatchNorm in SmallRAFT."""
 
     def forward(self, image1, image2, iters=12, flow_init=None, last_only=False):
-        self._check(image1, image2, iters, flow_init)
-        image1 = 2 * image1 - 1.0
-        image2 = 2 * image2 - 1.0
-        hdim, cdim = self.hidden_dim, self.context_dim
-        fmap1, fmap2 = self.fnet([image1, image2])
-        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
-        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
-        cnet = self.cnet(image1)
-        net, inp = torch.split(cnet, [hdim, cdim], dim=1)
-        net = conv._nhwc(torch.tanh(net))
-        inp = conv._nhwc(torch.relu(inp))                   # made once: the update block's hoisted term is keyed on this object
-        B, _, H, W = image1.shape
-        coords0 = coords_grid(B, H // 8, W // 8, image1.device)
-        coords1 = coords0
-        if flow_init is not None:
-            coords1 = coords1 + flow_init
-        flows = []
-        for _ in range(int(iters)):
-            coords1 = coords1.detach()
-            corr = corr_fn(coords1, memory_format=CL)
-            flow = coords1 - coords0
-            net, _, delta_flow = self.update_block(net, inp, corr, flow)
-            coords1 = coords1 + delta_flow
-            flows.append(coords1 - coords0)
-        self.flow_low = [f.detach() for f in flows]         # the 1/8-resolution flows of the last call (RAFT's test_mode output)
-        if last_only:
-            return [upflow8(flows[-1])]
-        return list(torch.split(upflow8(torch.cat(flows, 0)), B, dim=0))
+        flows, _ = self._iterate(image1, image2, iters, flow_init)
+        return self._upsampled(flows, None, last_only)

@@ -24,8 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import CorrCfg, DvsError, check, ptr
-
-CL = torch.channels_last
+from ._raft_host import CL, gpu_arg
 
 
 def _cfg(B, Cn, H, W, num_levels, radius, nchw1=0, nchw2=0):
@@ -40,14 +39,14 @@ class NoCpuPath(DvsError, NotImplementedError):
     and a NotImplementedError because that is what the alternate block of this package answered before it existed."""
 
 
-def _check_fmap(name, t, no_cpu=DvsError):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise no_cpu("%s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
-    if t.dtype != torch.float32:
-        raise DvsError("%s: fp32 only, got %s (the reference casts with .float() at raft.py:82-83 even under autocast)"
-                       % (name, t.dtype))
-    if t.dim() != 4:
-        raise DvsError("%s: [B,C,h,w] expected, got %s" % (name, tuple(t.shape)))
+def _check_fmaps(who, fmap1, fmap2, no_cpu=DvsError):
+    for name, t in (("fmap1", fmap1), ("fmap2", fmap2)):
+        gpu_arg("%s: %s" % (who, name), t, "[B,C,h,w] expected", no_cpu=no_cpu,
+                fp32_note=" (the reference casts with .float() at raft.py:82-83 even under autocast)")
+    if fmap1.shape != fmap2.shape:
+        raise DvsError("%s: fmap1 %s and fmap2 %s differ" % (who, tuple(fmap1.shape), tuple(fmap2.shape)))
+    if fmap2.device != fmap1.device:
+        raise DvsError("%s: fmap1 on %s, fmap2 on %s" % (who, fmap1.device, fmap2.device))
 
 
 def _sizes(cfg):
@@ -156,8 +155,7 @@ def _lookup_raw(state, coords, channels_last):
 
 
 def _check_coords(name, coords, cfg, device):
-    if not torch.is_tensor(coords) or not coords.is_cuda:
-        raise DvsError("%s: GPU coordinates only; this package has no CPU path" % name)
+    gpu_arg(name + ": coords", coords, "[B,2,h,w] expected")
     if coords.device != device:
         raise DvsError("%s: coords on %s, the block on %s" % (name, coords.device, device))
     if coords.requires_grad:
@@ -165,8 +163,6 @@ def _check_coords(name, coords, cfg, device):
                        "(coords1 = coords1.detach()); pass coords.detach()" % name)
     if tuple(coords.shape) != (cfg.B, 2, cfg.H, cfg.W):
         raise DvsError("%s: coords must be [%d,2,%d,%d], got %s" % (name, cfg.B, cfg.H, cfg.W, tuple(coords.shape)))
-    if coords.dtype != torch.float32:
-        raise DvsError("%s: fp32 coordinates only, got %s" % (name, coords.dtype))
     return coords.contiguous()
 
 
@@ -182,12 +178,7 @@ class CorrBlock:
     """model/raft/core/corr.py:12-60.  `corr_pyramid[i]` is a [B*h*w, 1, h>>i, w>>i] view of the one pyramid buffer."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        _check_fmap("CorrBlock: fmap1", fmap1)
-        _check_fmap("CorrBlock: fmap2", fmap2)
-        if fmap1.shape != fmap2.shape:
-            raise DvsError("CorrBlock: fmap1 %s and fmap2 %s differ" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-        if fmap2.device != fmap1.device:
-            raise DvsError("CorrBlock: fmap1 on %s, fmap2 on %s" % (fmap1.device, fmap2.device))
+        _check_fmaps("CorrBlock", fmap1, fmap2)
         B, Cn, H, W = fmap1.shape
         _sizes(_cfg(B, Cn, H, W, num_levels, radius))               # every shape limit, before anything is allocated
         self.num_levels, self.radius = int(num_levels), int(radius)
@@ -312,12 +303,7 @@ class AlternateCorrBlock:
     the pooled rows of fmap2 -- (1 + 1/4 + ...) feature maps, not a volume."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        _check_fmap("AlternateCorrBlock: fmap1", fmap1, NoCpuPath)
-        _check_fmap("AlternateCorrBlock: fmap2", fmap2, NoCpuPath)
-        if fmap1.shape != fmap2.shape:
-            raise DvsError("AlternateCorrBlock: fmap1 %s and fmap2 %s differ" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-        if fmap2.device != fmap1.device:
-            raise DvsError("AlternateCorrBlock: fmap1 on %s, fmap2 on %s" % (fmap1.device, fmap2.device))
+        _check_fmaps("AlternateCorrBlock", fmap1, fmap2, NoCpuPath)
         B, Cn, H, W = fmap1.shape
         self.num_levels, self.radius = int(num_levels), int(radius)
         _alt_sizes(_cfg(B, Cn, H, W, self.num_levels, self.radius))    # every shape limit, before anything is allocated

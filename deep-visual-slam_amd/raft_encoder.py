@@ -20,32 +20,19 @@ GPU and fp32 only; no host synchronisation in forward or backward.
 BasicEncoder (extractor.py:118-192, full-size RAFT's fnet and cnet) follows further down: ResidualBlock stacks with the same
 tail kernel, and norm_fn='batch' on the BatchNorm kernels of bn.py.
 """
-import weakref
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, conv, nn_ops
+from . import _lib, conv
 from . import bn as _bn_ops
 from ._lib import DvsError, check
-from .raft_update import _drop_on_gradient
-
-CL = torch.channels_last
+from ._raft_host import CL, DerivedOperands, gpu_arg
 
 
 def slice_pixels():
     """T: the pixels of one slice of csrc/inorm.hip (one workgroup's share of an image)."""
     return int(_lib.lib().dvs_inorm_slice_pixels())
-
-
-def _check_map(name, t):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise DvsError("%s: GPU tensors only (got %s); this package has no CPU path" % (name, getattr(t, "device", type(t))))
-    if t.dtype != torch.float32:
-        raise DvsError("%s: fp32 only, got %s" % (name, t.dtype))
-    if t.dim() != 4:
-        raise DvsError("%s: [N,C,H,W] expected, got %s" % (name, tuple(t.shape)))
 
 
 def _workspace(N, HW, Cn, device):
@@ -93,7 +80,7 @@ class _InormAct(torch.autograd.Function):
 def instance_norm_act(y, norm=True, relu=True, residual=None):
     """The fused tail (module docstring) of a [N,C,H,W] fp32 GPU tensor, differentiable in y and residual.  The result is in
     channels_last memory."""
-    _check_map("instance_norm_act: y", y)
+    gpu_arg("instance_norm_act: y", y, "[N,C,H,W] expected")
     N, Cn, H, W = y.shape
     if Cn % 4 or Cn < 4 or Cn > 1024:
         raise DvsError("instance_norm_act: C=%d must be a multiple of 4 in 4 .. 1024 (16-byte channel groups)" % Cn)
@@ -101,7 +88,7 @@ def instance_norm_act(y, norm=True, relu=True, residual=None):
         raise DvsError("instance_norm_act: %s: instance norm needs more than one spatial element per image (torch rejects it too)"
                        % (tuple(y.shape),))
     if residual is not None:
-        _check_map("instance_norm_act: residual", residual)
+        gpu_arg("instance_norm_act: residual", residual, "[N,C,H,W] expected")
         if residual.shape != y.shape or residual.device != y.device:
             raise DvsError("instance_norm_act: residual %s on %s, y %s on %s"
                            % (tuple(residual.shape), residual.device, tuple(y.shape), y.device))
@@ -109,6 +96,96 @@ def instance_norm_act(y, norm=True, relu=True, residual=None):
 
 
 # ---- the encoder ---------------------------------------------------------------------------------------------------------------
+def _image4(x):
+    """The image in NHWC memory with a zero fourth channel."""
+    return F.pad(x.permute(0, 2, 3, 1), (0, 1)).permute(0, 3, 1, 2)
+
+
+class _Encoder(DerivedOperands, nn.Module):
+    """What the two encoders share (extractor.py:118-192, 195-267): conv1 7x7/2, three stages of two blocks, conv2 1x1.  A subclass
+    names its blocks' convolutions in BLOCK_CONVS and provides _block(b, w, x)."""
+    BLOCK_CONVS = ()
+
+    def _build(self, widths, output_dim, block):
+        """conv1, layer1 .. layer3 of two block(in_planes, planes, stride) each, conv2, in the reference's order and with its init
+        (extractor.py:150-157, 226-228)."""
+        if int(output_dim) <= 0 or int(output_dim) % 4:
+            raise DvsError("%s: output_dim=%r must be a positive multiple of 4" % (type(self).__name__, output_dim))
+        self.conv1 = nn.Conv2d(3, widths[0], kernel_size=7, stride=2, padding=3)
+        planes = widths[0]
+        for i, (dim, stride) in enumerate(zip(widths, (1, 2, 2)), 1):
+            setattr(self, "layer%d" % i, nn.Sequential(block(planes, dim, stride), block(dim, dim, 1)))
+            planes = dim
+        self.conv2 = nn.Conv2d(planes, int(output_dim), kernel_size=1)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        self._drop()
+
+    def _blocks(self):
+        return [b for i in (1, 2, 3) for b in getattr(self, "layer%d" % i)]
+
+    def _convs(self):
+        out = [self.conv1]
+        for b in self._blocks():
+            out += [getattr(b, n) for n in self.BLOCK_CONVS] + ([b.downsample[0]] if b.downsample is not None else [])
+        return out + [self.conv2]
+
+    def _padding(self, m):
+        """(zero input channels, zero output channels) that convolution `m` runs with: conv1 reads the 4-channel image."""
+        return (1 if m is self.conv1 else 0), 0
+
+    def _operands(self):
+        """{conv module: (channels_last weight, bias)}, zero-padded by self._padding."""
+        w = {}
+        for m in self._convs():
+            wt, b = m.weight, m.bias
+            pad_i, pad_o = self._padding(m)
+            if pad_i or pad_o:
+                wt = F.pad(wt, (0, 0, 0, 0, 0, pad_i, 0, pad_o))
+            if pad_o:
+                b = F.pad(b, (0, pad_o))
+            w[m] = (wt.contiguous(memory_format=CL), b)
+        return w, [t for pair in w.values() for t in pair]
+
+    def _unit(self, x, w, m, norm, stride=1, padding=0, relu=True):
+        """[relu](norm(conv m)); `norm` is the norm's module, which only the 'batch' form reads."""
+        wt, b = w[m]
+        if self.norm_fn == "instance":
+            return instance_norm_act(conv.conv2d(x, wt, b, stride=stride, padding=padding), relu=relu)
+        return conv.conv2d(x, wt, b, stride=stride, padding=padding, act="relu" if relu else None)
+
+    def forward(self, x):
+        who = type(self).__name__
+        is_list = isinstance(x, (tuple, list))
+        if is_list:
+            if len(x) != 2:
+                raise DvsError("%s: a list input holds two image batches (extractor.py:171-174, 246-265), got %d" % (who, len(x)))
+            for t in x:
+                gpu_arg(who + ": input", t, "[N,C,H,W] expected")
+            if x[0].shape != x[1].shape:
+                raise DvsError("%s: the two batches differ: %s and %s" % (who, tuple(x[0].shape), tuple(x[1].shape)))
+            batch_dim = x[0].shape[0]
+            x = torch.cat(list(x), 0)
+        gpu_arg(who + ": input", x, "[N,C,H,W] expected")
+        if x.shape[1] != 3:
+            raise DvsError("%s: 3 input channels expected, got %s" % (who, tuple(x.shape)))
+        if x.shape[2] < 16 or x.shape[3] < 16:
+            raise DvsError("%s: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (who, tuple(x.shape)))
+        for p in self.parameters():
+            if p.device != x.device or p.dtype != torch.float32:
+                raise DvsError("%s: parameters on %s / %s, input on %s / fp32; move the module with .to()"
+                               % (who, p.device, p.dtype, x.device))
+        w = self._derive()
+        x = self._unit(_image4(x), w, self.conv1, getattr(self, "norm1", None), 2, 3)
+        for b in self._blocks():
+            x = self._block(b, w, x)
+        x = conv.conv2d(x, *w[self.conv2])
+        if is_list:
+            return torch.split(x, [batch_dim, batch_dim], dim=0)
+        return x
+
+
 class _Bottleneck(nn.Module):
     """Holds the parameters of one BottleneckBlock (extractor.py:60-104) under the reference's names."""
 
@@ -121,102 +198,29 @@ class _Bottleneck(nn.Module):
         self.downsample = None if stride == 1 else nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride))
 
 
-class SmallEncoder(nn.Module):
+class SmallEncoder(_Encoder):
+    BLOCK_CONVS = ("conv1", "conv2", "conv3")
+
     def __init__(self, output_dim=128, norm_fn="instance", dropout=0.0):
         super().__init__()
         if norm_fn not in ("instance", "none"):
             raise DvsError("SmallEncoder: norm_fn=%r is not built: SmallRAFT uses 'instance' (fnet) and 'none' (cnet) only" % (norm_fn,))
         if dropout and dropout > 0:
             raise DvsError("SmallEncoder: dropout=%r is not built: SmallRAFT forces it to 0 (raft.py:29)" % (dropout,))
-        if int(output_dim) <= 0 or int(output_dim) % 4:
-            raise DvsError("SmallEncoder: output_dim=%r must be a positive multiple of 4" % (output_dim,))
         self.norm_fn = norm_fn
-        self.conv1 = nn.Conv2d(3, 32, kernel_size=7, stride=2, padding=3)
-        planes = 32
-        for i, (dim, stride) in enumerate(((32, 1), (64, 2), (96, 2)), 1):
-            setattr(self, "layer%d" % i, nn.Sequential(_Bottleneck(planes, dim, stride), _Bottleneck(dim, dim, 1)))
-            planes = dim
-        self.conv2 = nn.Conv2d(96, int(output_dim), kernel_size=1)
-        for m in self.modules():                                        # extractor.py:226-228
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-        self._weights = self._context = None
-
-    def _blocks(self):
-        return [b for i in (1, 2, 3) for b in getattr(self, "layer%d" % i)]
-
-    def _convs(self):
-        out = [self.conv1]
-        for b in self._blocks():
-            out += [b.conv1, b.conv2, b.conv3] + ([b.downsample[0]] if b.downsample is not None else [])
-        return out + [self.conv2]
-
-    def _derive(self):
-        """{conv module: (channels_last weight, bias)}, conv1's filter zero-padded to 4 input channels: made by differentiable
-        torch ops and kept under raft_update's stamp rule (parameter versions and nn_ops.generation(), which dp.FusedAdam bumps)."""
-        stamp = (torch.is_grad_enabled(), nn_ops.generation()) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
-        if self._weights is not None and self._weights[0] == stamp:
-            return self._weights[1]
-        w = {}
-        for m in self._convs():
-            wt = F.pad(m.weight, (0, 0, 0, 0, 0, 1)) if m is self.conv1 else m.weight
-            w[m] = (wt.contiguous(memory_format=CL), m.bias)
-        self._weights = (stamp, w)
-        if torch.is_grad_enabled():
-            hook = _drop_on_gradient(weakref.ref(self))     # their graph is freed by the backward pass that delivers these gradients
-            for wt, _ in w.values():
-                if wt.requires_grad and not wt.is_leaf:
-                    wt.register_hook(hook)
-        return w
+        self._build((32, 64, 96), output_dim, _Bottleneck)
 
     def _block(self, b, w, x):
         norm = self.norm_fn == "instance"
         s = b.stride
-        if norm:
-            y = instance_norm_act(conv.conv2d(x, *w[b.conv1]))
-            y = instance_norm_act(conv.conv2d(y, *w[b.conv2], stride=s, padding=1))
-        else:
-            y = conv.conv2d(x, *w[b.conv1], act="relu")
-            y = conv.conv2d(y, *w[b.conv2], stride=s, padding=1, act="relu")
+        y = self._unit(x, w, b.conv1, None)
+        y = self._unit(y, w, b.conv2, None, s, 1)
         y = conv.conv2d(y, *w[b.conv3])
         if b.downsample is not None:
             x = conv.conv2d(x, *w[b.downsample[0]], stride=s)
             if norm:
                 x = instance_norm_act(x, relu=False)
         return instance_norm_act(y, norm=norm, relu=True, residual=x)          # relu(x + relu(norm3(conv3(.)))), extractor.py:111-116
-
-    def forward(self, x):
-        is_list = isinstance(x, (tuple, list))
-        if is_list:
-            if len(x) != 2:
-                raise DvsError("SmallEncoder: a list input holds two image batches (extractor.py:246-265), got %d" % len(x))
-            for t in x:
-                _check_map("SmallEncoder: input", t)
-            if x[0].shape != x[1].shape:
-                raise DvsError("SmallEncoder: the two batches differ: %s and %s" % (tuple(x[0].shape), tuple(x[1].shape)))
-            batch_dim = x[0].shape[0]
-            x = torch.cat(list(x), 0)
-        _check_map("SmallEncoder: input", x)
-        if x.shape[1] != 3:
-            raise DvsError("SmallEncoder: 3 input channels expected, got %s" % (tuple(x.shape),))
-        if x.shape[2] < 16 or x.shape[3] < 16:
-            raise DvsError("SmallEncoder: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (tuple(x.shape),))
-        for p in self.parameters():
-            if p.device != x.device or p.dtype != torch.float32:
-                raise DvsError("SmallEncoder: parameters on %s / %s, input on %s / fp32; move the module with .to()"
-                               % (p.device, p.dtype, x.device))
-        w = self._derive()
-        x4 = F.pad(x.permute(0, 2, 3, 1), (0, 1)).permute(0, 3, 1, 2)           # NHWC memory, a zero fourth channel
-        if self.norm_fn == "instance":
-            x = instance_norm_act(conv.conv2d(x4, *w[self.conv1], stride=2, padding=3))
-        else:
-            x = conv.conv2d(x4, *w[self.conv1], stride=2, padding=3, act="relu")
-        for b in self._blocks():
-            x = self._block(b, w, x)
-        x = conv.conv2d(x, *w[self.conv2])
-        if is_list:
-            return torch.split(x, [batch_dim, batch_dim], dim=0)
-        return x
 
 
 # ---- the full-size encoder -----------------------------------------------------------------------------------------------------
@@ -239,7 +243,7 @@ class _Residual(nn.Module):
         self.downsample = None if stride == 1 else nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride), self.norm3)
 
 
-class BasicEncoder(nn.Module):
+class BasicEncoder(_Encoder):
     """extractor.py:118-192: conv1 7x7/2 3->64, norm, ReLU, three stages of two ResidualBlocks (64, 96/2, 128/2), conv2 1x1.
 
     norm_fn 'instance' (RAFT's fnet) and 'none' run as SmallEncoder does.  'batch' (RAFT's cnet) runs on bn.bn_act in train mode
@@ -253,6 +257,8 @@ class BasicEncoder(nn.Module):
     statistics are padded by differentiable torch ops, the padded channels stay exactly zero through ReLU, the residual adds and
     the next stage's zero input filters, and their gradients are dropped by the padding's backward."""
 
+    BLOCK_CONVS = ("conv1", "conv2")
+
     def __init__(self, output_dim=128, norm_fn="batch", dropout=0.0):
         super().__init__()
         if norm_fn not in ("instance", "batch", "none"):
@@ -260,56 +266,20 @@ class BasicEncoder(nn.Module):
                            % (norm_fn,))
         if dropout and dropout > 0:
             raise DvsError("BasicEncoder: dropout=%r is not built: train with dropout=0 (the released RAFT checkpoints do)" % (dropout,))
-        if int(output_dim) <= 0 or int(output_dim) % 4:
-            raise DvsError("BasicEncoder: output_dim=%r must be a positive multiple of 4" % (output_dim,))
         self.norm_fn = norm_fn
         self.norm1 = nn.BatchNorm2d(64) if norm_fn == "batch" else nn.Sequential()
-        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
-        planes = 64
-        for i, (dim, stride) in enumerate(((64, 1), (96, 2), (128, 2)), 1):
-            setattr(self, "layer%d" % i, nn.Sequential(_Residual(planes, dim, norm_fn, stride), _Residual(dim, dim, norm_fn, 1)))
-            planes = dim
-        self.conv2 = nn.Conv2d(128, int(output_dim), kernel_size=1)
-        for m in self.modules():                                        # extractor.py:150-157
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-        self._weights = self._context = None
+        self._build((64, 96, 128), output_dim, lambda in_planes, planes, stride: _Residual(in_planes, planes, norm_fn, stride))
 
-    def _blocks(self):
-        return [b for i in (1, 2, 3) for b in getattr(self, "layer%d" % i)]
-
-    def _convs(self):
-        out = [self.conv1]
-        for b in self._blocks():
-            out += [b.conv1, b.conv2] + ([b.downsample[0]] if b.downsample is not None else [])
-        return out + [self.conv2]
-
-    def _derive(self):
-        """{conv module: (channels_last weight, bias)} under SmallEncoder's stamp rule.  conv1's filter is zero-padded to 4 input
-        channels; in the 'batch' form every 96 becomes 128 (zero filters, zero input channels, zero biases)."""
-        stamp = (torch.is_grad_enabled(), nn_ops.generation()) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
-        if self._weights is not None and self._weights[0] == stamp:
-            return self._weights[1]
-        wide = (lambda c: BN_WIDTH.get(c, c)) if self.norm_fn == "batch" else (lambda c: c)
-        w = {}
-        for m in self._convs():
-            wt, b = m.weight, m.bias
-            co, ci = wt.shape[:2]
-            pad_o = (wide(co) - co) if m is not self.conv2 else 0
-            pad_i = 1 if m is self.conv1 else wide(ci) - ci
-            if pad_o or pad_i:
-                wt = F.pad(wt, (0, 0, 0, 0, 0, pad_i, 0, pad_o))
-            if pad_o:
-                b = F.pad(b, (0, pad_o))
-            w[m] = (wt.contiguous(memory_format=CL), b)
-        self._weights = (stamp, w)
-        if torch.is_grad_enabled():
-            hook = _drop_on_gradient(weakref.ref(self))     # their graph is freed by the backward pass that delivers these gradients
-            for wt, b in w.values():
-                for t in (wt, b):
-                    if t.requires_grad and not t.is_leaf:
-                        t.register_hook(hook)
-        return w
+    def _padding(self, m):
+        """In the 'batch' form every 96 becomes 128 as well: zero filters, zero input channels, zero biases."""
+        pad_i, pad_o = super()._padding(m)
+        if self.norm_fn == "batch":
+            co, ci = m.weight.shape[:2]
+            if m is not self.conv1:
+                pad_i = BN_WIDTH.get(ci, ci) - ci
+            if m is not self.conv2:
+                pad_o = BN_WIDTH.get(co, co) - co
+        return pad_i, pad_o
 
     # ---- conv -> norm -> ReLU, by norm_fn --------------------------------------------------------------------------------------
     def _bn(self, y_conv, bias, bn, relu):
@@ -338,12 +308,10 @@ class BasicEncoder(nn.Module):
         return _bn_ops.affine_act(y, scale, shift + bias * scale, relu=relu)
 
     def _unit(self, x, w, m, norm, stride=1, padding=0, relu=True):
-        wt, b = w[m]
-        if self.norm_fn == "instance":
-            return instance_norm_act(conv.conv2d(x, wt, b, stride=stride, padding=padding), relu=relu)
         if self.norm_fn == "batch":
+            wt, b = w[m]
             return self._bn((x, wt, stride, padding), b, norm, relu)
-        return conv.conv2d(x, wt, b, stride=stride, padding=padding, act="relu" if relu else None)
+        return super()._unit(x, w, m, norm, stride, padding, relu)
 
     def _block(self, b, w, x):
         s = b.stride
@@ -355,36 +323,6 @@ class BasicEncoder(nn.Module):
             return instance_norm_act(conv.conv2d(y, wt, bias, padding=1), norm=True, relu=True, residual=x)
         y = self._unit(y, w, b.conv2, b.norm2, 1, 1)
         return instance_norm_act(y, norm=False, relu=False, residual=x)      # relu(x + y), extractor.py:56
-
-    def forward(self, x):
-        is_list = isinstance(x, (tuple, list))
-        if is_list:
-            if len(x) != 2:
-                raise DvsError("BasicEncoder: a list input holds two image batches (extractor.py:171-174), got %d" % len(x))
-            for t in x:
-                _check_map("BasicEncoder: input", t)
-            if x[0].shape != x[1].shape:
-                raise DvsError("BasicEncoder: the two batches differ: %s and %s" % (tuple(x[0].shape), tuple(x[1].shape)))
-            batch_dim = x[0].shape[0]
-            x = torch.cat(list(x), 0)
-        _check_map("BasicEncoder: input", x)
-        if x.shape[1] != 3:
-            raise DvsError("BasicEncoder: 3 input channels expected, got %s" % (tuple(x.shape),))
-        if x.shape[2] < 16 or x.shape[3] < 16:
-            raise DvsError("BasicEncoder: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (tuple(x.shape),))
-        for p in self.parameters():
-            if p.device != x.device or p.dtype != torch.float32:
-                raise DvsError("BasicEncoder: parameters on %s / %s, input on %s / fp32; move the module with .to()"
-                               % (p.device, p.dtype, x.device))
-        w = self._derive()
-        x4 = F.pad(x.permute(0, 2, 3, 1), (0, 1)).permute(0, 3, 1, 2)           # NHWC memory, a zero fourth channel
-        x = self._unit(x4, w, self.conv1, self.norm1, 2, 3)
-        for b in self._blocks():
-            x = self._block(b, w, x)
-        x = conv.conv2d(x, *w[self.conv2])
-        if is_list:
-            return torch.split(x, [batch_dim, batch_dim], dim=0)
-        return x
 
 
 class _TrainBN:

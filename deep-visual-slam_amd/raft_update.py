@@ -24,16 +24,14 @@ BasicUpdateBlock (update.py:114-136) is the same split, twice: SepConvGRU's (1,5
 over shift_stack(x, axis), the five shifted copies of x side by side along the channels (csrc/shiftstack.hip), with the filter
 re-laid by stacked_filter; the gate kernels are the same four.
 """
-import weakref
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, conv, nn_ops
+from . import _lib, conv
 from ._lib import DvsError, check
+from ._raft_host import CL, DerivedOperands, gpu_arg
 
-CL = torch.channels_last
 CTX_DIM = 64            # channels of `inp` (SmallRAFT's context_dim, raft.py:34)
 MOTION_DIM = 82         # SmallMotionEncoder's 80 + the 2 flow channels (update.py:77)
 
@@ -159,28 +157,65 @@ def conv_gru(a_h, a_x, c, h, conv_q):
 
 
 class _Weights:
-    """The kernels' view of the eighteen parameters: channels_last, the GRU's three filters stacked and cut by input block."""
-    __slots__ = ("c1", "f1", "f2", "m", "gh", "gq", "gx", "gc", "h1", "h2")
+    """The kernels' view of the eighteen parameters: channels_last, the GRU's three filters stacked and cut by input block.
+    cor and flo are the motion encoder's two chains of (filter, bias), m its closing convolution."""
+    __slots__ = ("cor", "flo", "m", "gh", "gq", "gx", "gc", "h1", "h2")
 
 
-def _drop_on_gradient(owner_ref):
-    def hook(grad):
-        owner = owner_ref()
-        if owner is not None:
-            owner._weights = owner._context = None
-    return hook
+def _cl(t):
+    return t.contiguous(memory_format=CL)
 
 
-class _UpdateBlock(nn.Module):
-    """What the two update blocks share: the parameter holders under the reference's names, the stamp rule of the derived
-    operands and the per-context cache of the hoisted terms.  A subclass sets CTX (channels of `inp`) and provides _derive()
-    and _context_terms(inp, w)."""
-    CTX = None
+def _pad_in(t, n):
+    """A filter with n zero input channels behind its own."""
+    return F.pad(t, (0, 0, 0, 0, 0, n))
 
-    def _make_groups(self, layout, source):
-        """layout {group: [(name, Cout, Cin, k, padding)]}, k an int or (kh, kw): nn.Conv2d holders with the reference's init, or,
-        with `source`, holders that share the Parameter objects of a block of the reference's shape."""
+
+def _flow4(flow):
+    """flow as a NHWC tensor with two zero channels behind its own: 4 channels for convf1."""
+    return F.pad(flow.permute(0, 2, 3, 1), (0, 2)).contiguous().permute(0, 3, 1, 2)
+
+
+def _chain(x, layers):
+    """relu(conv(.)) through `layers` of (filter, bias), each padded to keep the map's size."""
+    for wt, b in layers:
+        x = conv.conv2d(x, wt, b, padding=wt.shape[2] // 2, act="relu")
+    return x
+
+
+class _UpdateBlock(DerivedOperands, nn.Module):
+    """One update step (update.py:99-136) up to what differs between the two blocks.  Here: the parameter holders under the
+    reference's names, the cache of the derived operands and of the hoisted context terms (_raft_host.DerivedOperands), the input
+    checks, the motion encoder and the flow head.  A subclass sets CTX (channels of `inp`) and GATE (the gate convolution whose
+    width is hidden_dim) and provides _layout(hidden, planes), _operands(), _context_terms(inp, w) and its GRU in forward."""
+    CTX = GATE = None
+
+    def __init__(self, hidden_dim, corr_levels, corr_radius):
+        super().__init__()
+        self._setup(int(hidden_dim), int(corr_levels) * (2 * int(corr_radius) + 1) ** 2, None)
+
+    @classmethod
+    def from_module(cls, block):
+        """Wrap a block of the reference's shape (duck typing: .encoder / .gru / .flow_head [/ .mask] with the class's
+        convolutions), sharing its Parameter objects."""
+        try:
+            hidden, planes = getattr(block.gru, cls.GATE).weight.shape[0], block.encoder.convc1.weight.shape[1]
+        except AttributeError as e:
+            raise DvsError("%s.from_module: not a %s (%s)" % (cls.__name__, cls.__name__, e))
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._setup(int(hidden), int(planes), block)
+        return self
+
+    def _setup(self, hidden, planes, source):
+        """self._layout's {group: [(name, Cout, Cin, k, padding)]}, k an int or (kh, kw): nn.Conv2d holders with the reference's
+        init, or, with `source`, holders that share the Parameter objects of a block of the reference's shape."""
         who = type(self).__name__
+        layout = self._layout(hidden, planes)               # refuses a hidden_dim the block cannot run
+        if planes <= 0 or planes % 4:
+            raise DvsError("%s: corr_levels * (2 * corr_radius + 1)^2 = %d correlation planes must be a multiple of 4 (the "
+                           "reference's settings give 196 and 324)" % (who, planes))
+        self.hidden_dim, self.cor_planes = hidden, planes
         for group, convs in layout.items():
             holder = nn.Module()
             for name, co, ci, k, pad in convs:
@@ -199,54 +234,13 @@ class _UpdateBlock(nn.Module):
                     layer.weight, layer.bias = w, b
                 setattr(holder, name, layer)
             setattr(self, group, holder)
-        self._weights = self._context = None
+        self._drop()
 
-    # ---- what is made once per context ------------------------------------------------------------------------------------
-    def _stamp(self):
-        """conv._p16_stamp's rule over every parameter (dp.FusedAdam writes weights behind torch's back), plus what decides
-        whether the derived tensors are graph nodes."""
-        gen = nn_ops.generation()
-        return (torch.is_grad_enabled(), gen) + tuple((id(p), p._version, p.requires_grad) for p in self.parameters())
-
-    def _keep(self, stamp, w, tensors):
-        """Serve the derived operands `w` while the stamp holds; `tensors`: the derived tensors themselves."""
-        self._weights, self._context = (stamp, w), None
-        if torch.is_grad_enabled():
-            # their graph is freed by the backward pass that delivers these gradients: never serve them again after it
-            hook = _drop_on_gradient(weakref.ref(self))
-            for t in tensors:
-                if t.requires_grad and not t.is_leaf:
-                    t.register_hook(hook)
-        return w
-
-    def _hoisted(self, inp, w):
-        """The terms that depend on `inp` and the weights alone (self._context_terms): reused while `inp` is the same tensor
-        object with the same version and requires_grad, and the weights (self._derive's stamp, which includes the grad mode) are
-        the same."""
-        ent = self._context
-        key = (inp._version, inp.requires_grad)
-        if ent is not None and ent[0]() is inp and ent[1] == key:
-            return ent[2]
-        c = self._context_terms(inp, w)
-        hook = _drop_on_gradient(weakref.ref(self))
-        for t in (c if isinstance(c, tuple) else (c,)):
-            if t.requires_grad:
-                t.register_hook(hook)
-        self._context = (weakref.ref(inp), key, c)
-        return c
-
-    # ---- input checks -----------------------------------------------------------------------------------------------------
     def _check(self, net, inp, corr, flow):
         who = type(self).__name__
         want = (("net", net, self.hidden_dim), ("inp", inp, self.CTX), ("corr", corr, self.cor_planes), ("flow", flow, 2))
         for name, t, _ in want:
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DvsError("%s: %s: GPU tensors only (got %s); this package has no CPU path"
-                               % (who, name, getattr(t, "device", type(t))))
-            if t.dtype != torch.float32:
-                raise DvsError("%s: %s: fp32 only, got %s" % (who, name, t.dtype))
-            if t.dim() != 4:
-                raise DvsError("%s: %s: [B,C,H,W] expected, got %s" % (who, name, tuple(t.shape)))
+            gpu_arg("%s: %s" % (who, name), t, "[B,C,H,W] expected")
         B, _, H, W = net.shape
         for name, t, ch in want:
             if tuple(t.shape) != (B, ch, H, W):
@@ -258,63 +252,54 @@ class _UpdateBlock(nn.Module):
                 raise DvsError("%s: parameters on %s / %s, inputs on %s / fp32; move the block with .to()"
                                % (who, p.device, p.dtype, net.device))
 
+    def _enter(self, net, inp, corr, flow):
+        """What a step does before its GRU: (operands, hoisted terms, net in NHWC memory, the motion encoder's output
+        (update.py:71-77, 89-97) without the flow, the 4-channel flow)."""
+        self._check(net, inp, corr, flow)
+        w = self._derive()
+        c = self._hoisted(inp, w)                           # reused while `inp` is the same tensor object and the weights stand
+        net = conv._nhwc(net)
+        flow4 = _flow4(flow)
+        cor, flo = _chain(corr, w.cor), _chain(flow4, w.flo)
+        return w, c, net, conv.conv2d(torch.cat([cor, flo], 1), *w.m, padding=1, act="relu"), flow4
+
+    @staticmethod
+    def _flow_head(w, net):
+        """update.py:13-14."""
+        return conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
+
 
 class SmallUpdateBlock(_UpdateBlock):
     """update.py:99-112 with the reference's parameter names: encoder.{convc1,convf1,convf2,conv}, gru.{convz,convr,convq},
     flow_head.{conv1,conv2}, each .weight / .bias."""
-    CTX = CTX_DIM
+    CTX, GATE = CTX_DIM, "convz"
 
     def __init__(self, hidden_dim=96, corr_levels=4, corr_radius=3):
-        super().__init__()
-        self._setup(int(hidden_dim), int(corr_levels) * (2 * int(corr_radius) + 1) ** 2, None)
+        super().__init__(hidden_dim, corr_levels, corr_radius)
 
-    @classmethod
-    def from_module(cls, block):
-        """Wrap a block of the reference's shape (duck typing: .encoder / .gru / .flow_head with the convolutions above), sharing
-        its Parameter objects."""
-        try:
-            hidden, planes = block.gru.convz.weight.shape[0], block.encoder.convc1.weight.shape[1]
-        except AttributeError as e:
-            raise DvsError("SmallUpdateBlock.from_module: not a SmallUpdateBlock (%s)" % e)
-        self = cls.__new__(cls)
-        nn.Module.__init__(self)
-        self._setup(int(hidden), int(planes), block)
-        return self
-
-    def _setup(self, hidden, planes, source):
+    def _layout(self, hidden, planes):
         if hidden <= 0 or hidden % 4:
             raise DvsError("SmallUpdateBlock: hidden_dim=%d must be a positive multiple of 4 (16-byte channel groups)" % hidden)
-        if planes <= 0 or planes % 4:
-            raise DvsError("SmallUpdateBlock: corr_levels * (2 * corr_radius + 1)^2 = %d correlation planes must be a multiple "
-                           "of 4 (the reference's settings give 196 and 324)" % planes)
-        self.hidden_dim, self.cor_planes = hidden, planes
         gin = hidden + CTX_DIM + MOTION_DIM
-        self._make_groups({"encoder": [(n, co, ci if ci is not None else planes, k, k // 2) for n, co, ci, k in _ENCODER],
-                           "gru": [(n, hidden, gin, 3, 1) for n in ("convz", "convr", "convq")],
-                           "flow_head": [("conv1", 128, hidden, 3, 1), ("conv2", 2, 128, 3, 1)]}, source)
+        return {"encoder": [(n, co, ci if ci is not None else planes, k, k // 2) for n, co, ci, k in _ENCODER],
+                "gru": [(n, hidden, gin, 3, 1) for n in ("convz", "convr", "convq")],
+                "flow_head": [("conv1", 128, hidden, 3, 1), ("conv2", 2, 128, 3, 1)]}
 
-    def _derive(self):
-        """The operands of the launches, from the parameters, by differentiable torch ops."""
-        stamp = self._stamp()
-        if self._weights is not None and self._weights[0] == stamp:
-            return self._weights[1]
+    def _operands(self):
         hd = self.hidden_dim
         e, g, f = self.encoder, self.gru, self.flow_head
-        cl = lambda t: t.contiguous(memory_format=CL)
-        pad_in = lambda t, n: F.pad(t, (0, 0, 0, 0, 0, n))                      # zero input channels behind the real ones
         stack = torch.cat([g.convz.weight, g.convr.weight, g.convq.weight], 0)  # [3hd, hd + 64 + 82, 3, 3]
         w = _Weights()
-        w.c1 = (cl(e.convc1.weight), e.convc1.bias)
-        w.f1 = (cl(pad_in(e.convf1.weight, 2)), e.convf1.bias)                  # flow's 2 channels -> 4
-        w.f2 = (cl(e.convf2.weight), e.convf2.bias)
-        w.m = (cl(e.conv.weight), e.conv.bias)
-        w.gh = cl(stack[:2 * hd, :hd])
-        w.gq = cl(stack[2 * hd:, :hd])
-        w.gc = (cl(stack[:, hd:hd + CTX_DIM]), torch.cat([g.convz.bias, g.convr.bias, g.convq.bias]))
-        w.gx = cl(pad_in(stack[:, hd + CTX_DIM:], 2))                           # motion's 82 channels -> 84
-        w.h1 = (cl(f.conv1.weight), f.conv1.bias)
-        w.h2 = (cl(f.conv2.weight), f.conv2.bias)
-        return self._keep(stamp, w, (w.c1[0], w.f1[0], w.f2[0], w.m[0], w.gh, w.gq, w.gc[0], w.gc[1], w.gx, w.h1[0], w.h2[0]))
+        w.cor = ((_cl(e.convc1.weight), e.convc1.bias),)
+        w.flo = ((_cl(_pad_in(e.convf1.weight, 2)), e.convf1.bias), (_cl(e.convf2.weight), e.convf2.bias))   # flow's 2 channels -> 4
+        w.m = (_cl(e.conv.weight), e.conv.bias)
+        w.gh = _cl(stack[:2 * hd, :hd])
+        w.gq = _cl(stack[2 * hd:, :hd])
+        w.gc = (_cl(stack[:, hd:hd + CTX_DIM]), torch.cat([g.convz.bias, g.convr.bias, g.convq.bias]))
+        w.gx = _cl(_pad_in(stack[:, hd + CTX_DIM:], 2))                         # motion's 82 channels -> 84
+        w.h1 = (_cl(f.conv1.weight), f.conv1.bias)
+        w.h2 = (_cl(f.conv2.weight), f.conv2.bias)
+        return w, [p[0] for p in w.cor + w.flo + (w.m, w.h1, w.h2)] + [w.gh, w.gq, w.gc[0], w.gc[1], w.gx]
 
     def _context_conv(self, inp, weight, bias):
         """The hoisted convolution itself (tests count its calls)."""
@@ -324,27 +309,14 @@ class SmallUpdateBlock(_UpdateBlock):
         """c = conv(inp) + biases of the three gates, [B, 3hd, H, W]."""
         return self._context_conv(inp, *w.gc)
 
-    # ---- forward ----------------------------------------------------------------------------------------------------------
     def forward(self, net, inp, corr, flow):
-        self._check(net, inp, corr, flow)
-        w = self._derive()
-        c = self._hoisted(inp, w)
-        net = conv._nhwc(net)
-        # motion encoder (update.py:71-77).  flow goes in with 2 zero channels behind its own: 4 for convf1, and the same tensor
-        # closes the 80 + 2 motion channels to 84
-        flow4 = F.pad(flow.permute(0, 2, 3, 1), (0, 2)).contiguous().permute(0, 3, 1, 2)
-        cor = conv.conv2d(corr, *w.c1, act="relu")
-        flo = conv.conv2d(flow4, *w.f1, padding=3, act="relu")
-        flo = conv.conv2d(flo, *w.f2, padding=1, act="relu")
-        out = conv.conv2d(torch.cat([cor, flo], 1), *w.m, padding=1, act="relu")
-        motion = torch.cat([out, flow4], 1)
+        w, c, net, out, flow4 = self._enter(net, inp, corr, flow)
+        motion = torch.cat([out, flow4], 1)                 # the flow's two zero channels close the 80 + 2 motion channels to 84
         # ConvGRU (update.py:23-31), split by input block
         a_x = conv.conv2d(motion, w.gx, None, padding=1)
         a_h = conv.conv2d(net, w.gh, None, padding=1)
         net = conv_gru(a_h, a_x, c, net, lambda rh: conv.conv2d(rh, w.gq, None, padding=1))
-        # flow head (update.py:13-14)
-        delta_flow = conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
-        return net, None, delta_flow
+        return net, None, self._flow_head(w, net)
 
 
 # ---- the full-size block -------------------------------------------------------------------------------------------------------
@@ -371,12 +343,7 @@ def shift_stack(x, axis):
     """[B,5C,H,W] (channels_last memory) with channel t*C + c = x[:, c] moved by t - 2 along W (axis 0) or H (axis 1), zeros
     outside: a (1,5) / (5,1) convolution of x, padding (0,2) / (2,0), is the 1x1 convolution of this tensor with
     stacked_filter(weight).  fp32 GPU tensors, C % 4 == 0; differentiable."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise DvsError("shift_stack: GPU tensors only (got %s); this package has no CPU path" % (getattr(x, "device", type(x)),))
-    if x.dtype != torch.float32:
-        raise DvsError("shift_stack: fp32 only, got %s" % x.dtype)
-    if x.dim() != 4 or x.shape[1] % 4 or min(x.shape) < 1:
-        raise DvsError("shift_stack: [B,C,H,W] with C %% 4 == 0 expected, got %s" % (tuple(x.shape),))
+    gpu_arg("shift_stack", x, "[B,C,H,W] with C % 4 == 0 expected", ok=lambda s: s[1] % 4 == 0 and min(s) >= 1)
     if axis not in (0, 1):
         raise DvsError("shift_stack: axis=%r must be 0 (taps along W) or 1 (taps along H)" % (axis,))
     return _ShiftStack.apply(x, int(axis))
@@ -398,14 +365,14 @@ def split_gru_filters(wz, wr, wq, bz, br, bq, hidden, ctx):
     the stacked 1x1 filter: (gh [2hd] on stack(h), gq [hd] on stack(r*h), gc [3hd] on stack(inp), bias [3hd], gx [3hd] on
     stack(motion))."""
     stack = torch.cat([wz, wr, wq], 0)
-    cut = lambda t: stacked_filter(t).contiguous(memory_format=CL)
+    cut = lambda t: _cl(stacked_filter(t))
     return (cut(stack[:2 * hidden, :hidden]), cut(stack[2 * hidden:, :hidden]), cut(stack[:, hidden:hidden + ctx]),
             torch.cat([bz, br, bq]), cut(stack[:, hidden + ctx:]))
 
 
 class _BasicWeights:
     """The kernels' view of BasicUpdateBlock's parameters; gru[axis] = split_gru_filters of that pass."""
-    __slots__ = ("c1", "c2", "f1", "f2", "m", "gru", "h1", "h2", "m1", "m2")
+    __slots__ = ("cor", "flo", "m", "gru", "h1", "h2", "m1", "m2")
 
 
 class BasicUpdateBlock(_UpdateBlock):
@@ -416,66 +383,40 @@ class BasicUpdateBlock(_UpdateBlock):
     vertical pass whose (5,1) filters act on shift_stack(., 1), every contraction a 1x1 convolution with K = 5 * 128 on
     conv.conv2d.  Both passes' context terms are hoisted.  forward returns (net, mask, delta_flow); mask is the RAW output of the
     mask head, [B,576,H,W] in channels_last memory: the reference's 0.25 is raft.upsample_flow's mask_scale."""
-    CTX = 128
+    CTX, GATE = 128, "convz1"
     MASK_SCALE = 0.25       # update.py:135
 
     def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4):
-        super().__init__()
-        self._setup(int(hidden_dim), int(corr_levels) * (2 * int(corr_radius) + 1) ** 2, None)
+        super().__init__(hidden_dim, corr_levels, corr_radius)
 
-    @classmethod
-    def from_module(cls, block):
-        """Wrap a block of the reference's shape (.encoder / .gru / .flow_head / .mask), sharing its Parameter objects."""
-        try:
-            hidden, planes = block.gru.convz1.weight.shape[0], block.encoder.convc1.weight.shape[1]
-        except AttributeError as e:
-            raise DvsError("BasicUpdateBlock.from_module: not a BasicUpdateBlock (%s)" % e)
-        self = cls.__new__(cls)
-        nn.Module.__init__(self)
-        self._setup(int(hidden), int(planes), block)
-        return self
-
-    def _setup(self, hidden, planes, source):
+    def _layout(self, hidden, planes):
         if hidden != 128:
             raise DvsError("BasicUpdateBlock: hidden_dim=%d: the motion encoder's 128 channels and FlowHead(128, 256) fix it at 128 "
                            "(raft.py:134)" % hidden)
-        if planes <= 0 or planes % 4:
-            raise DvsError("BasicUpdateBlock: corr_levels * (2 * corr_radius + 1)^2 = %d correlation planes must be a multiple "
-                           "of 4 (the reference's settings give 196 and 324)" % planes)
-        self.hidden_dim, self.cor_planes = hidden, planes
         gin = hidden + self.CTX + 128
-        self._make_groups({
-            "encoder": [("convc1", 256, planes, 1, 0), ("convc2", 192, 256, 3, 1), ("convf1", 128, 2, 7, 3), ("convf2", 64, 128, 3, 1),
-                        ("conv", 126, 256, 3, 1)],
-            "gru": [(n + "1", hidden, gin, (1, 5), (0, 2)) for n in ("convz", "convr", "convq")]
-                   + [(n + "2", hidden, gin, (5, 1), (2, 0)) for n in ("convz", "convr", "convq")],
-            "flow_head": [("conv1", 256, hidden, 3, 1), ("conv2", 2, 256, 3, 1)],
-            "mask": [("0", 256, 128, 3, 1), ("2", 576, 256, 1, 0)]}, source)
+        return {"encoder": [("convc1", 256, planes, 1, 0), ("convc2", 192, 256, 3, 1), ("convf1", 128, 2, 7, 3),
+                            ("convf2", 64, 128, 3, 1), ("conv", 126, 256, 3, 1)],
+                "gru": [(n + "1", hidden, gin, (1, 5), (0, 2)) for n in ("convz", "convr", "convq")]
+                       + [(n + "2", hidden, gin, (5, 1), (2, 0)) for n in ("convz", "convr", "convq")],
+                "flow_head": [("conv1", 256, hidden, 3, 1), ("conv2", 2, 256, 3, 1)],
+                "mask": [("0", 256, 128, 3, 1), ("2", 576, 256, 1, 0)]}
 
-    def _derive(self):
-        stamp = self._stamp()
-        if self._weights is not None and self._weights[0] == stamp:
-            return self._weights[1]
-        hd = self.hidden_dim
+    def _operands(self):
         e, g, f = self.encoder, self.gru, self.flow_head
         m0, m2 = getattr(self.mask, "0"), getattr(self.mask, "2")
-        cl = lambda t: t.contiguous(memory_format=CL)
         w = _BasicWeights()
-        w.c1 = (cl(e.convc1.weight), e.convc1.bias)
-        w.c2 = (cl(e.convc2.weight), e.convc2.bias)
-        w.f1 = (cl(F.pad(e.convf1.weight, (0, 0, 0, 0, 0, 2))), e.convf1.bias)   # flow's 2 channels -> 4
-        w.f2 = (cl(e.convf2.weight), e.convf2.bias)
+        w.cor = ((_cl(e.convc1.weight), e.convc1.bias), (_cl(e.convc2.weight), e.convc2.bias))
+        w.flo = ((_cl(_pad_in(e.convf1.weight, 2)), e.convf1.bias), (_cl(e.convf2.weight), e.convf2.bias))   # flow's 2 channels -> 4
         # 126 outputs -> 128: two zero filters (and zero biases) whose relu(0) = 0 channels make room for the flow
-        w.m = (cl(F.pad(e.conv.weight, (0, 0, 0, 0, 0, 0, 0, 2))), F.pad(e.conv.bias, (0, 2)))
+        w.m = (_cl(F.pad(e.conv.weight, (0, 0, 0, 0, 0, 0, 0, 2))), F.pad(e.conv.bias, (0, 2)))
         w.gru = tuple(split_gru_filters(*(getattr(g, n + s).weight for n in ("convz", "convr", "convq")),
-                                        *(getattr(g, n + s).bias for n in ("convz", "convr", "convq")), hd, self.CTX)
+                                        *(getattr(g, n + s).bias for n in ("convz", "convr", "convq")), self.hidden_dim, self.CTX)
                       for s in ("1", "2"))
-        w.h1 = (cl(f.conv1.weight), f.conv1.bias)
-        w.h2 = (cl(f.conv2.weight), f.conv2.bias)
-        w.m1 = (cl(m0.weight), m0.bias)
-        w.m2 = (cl(m2.weight), m2.bias)
-        return self._keep(stamp, w, (w.c1[0], w.c2[0], w.f1[0], w.f2[0], w.m[0], w.m[1], w.h1[0], w.h2[0], w.m1[0], w.m2[0])
-                          + w.gru[0] + w.gru[1])
+        w.h1 = (_cl(f.conv1.weight), f.conv1.bias)
+        w.h2 = (_cl(f.conv2.weight), f.conv2.bias)
+        w.m1 = (_cl(m0.weight), m0.bias)
+        w.m2 = (_cl(m2.weight), m2.bias)
+        return w, [p[0] for p in w.cor + w.flo + (w.m, w.h1, w.h2, w.m1, w.m2)] + [w.m[1], *w.gru[0], *w.gru[1]]
 
     def _context_conv(self, stacked_inp, weight, bias):
         """One pass's hoisted convolution itself (tests count its calls)."""
@@ -486,26 +427,14 @@ class BasicUpdateBlock(_UpdateBlock):
         return tuple(self._context_conv(shift_stack(inp, axis), w.gru[axis][2], w.gru[axis][3]) for axis in (0, 1))
 
     def forward(self, net, inp, corr, flow, upsample=True):
-        self._check(net, inp, corr, flow)
-        w = self._derive()
-        c = self._hoisted(inp, w)
-        net = conv._nhwc(net)
-        # motion encoder (update.py:89-97); flow as the 4-channel NHWC tensor of SmallUpdateBlock
-        flow4 = F.pad(flow.permute(0, 2, 3, 1), (0, 2)).contiguous().permute(0, 3, 1, 2)
-        cor = conv.conv2d(corr, *w.c1, act="relu")
-        cor = conv.conv2d(cor, *w.c2, padding=1, act="relu")
-        flo = conv.conv2d(flow4, *w.f1, padding=3, act="relu")
-        flo = conv.conv2d(flo, *w.f2, padding=1, act="relu")
-        out = conv.conv2d(torch.cat([cor, flo], 1), *w.m, padding=1, act="relu")     # 128 channels, the last two zero
-        motion = torch.cat([out[:, :126], flow4[:, :2]], 1)                           # the flow takes their place
+        w, c, net, out, flow4 = self._enter(net, inp, corr, flow)
+        motion = torch.cat([out[:, :126], flow4[:, :2]], 1)     # `out` has 128 channels, the last two zero: the flow takes their place
         # SepConvGRU (update.py:45-60): horizontal, then vertical
         for axis in (0, 1):
             gh, gq, _, _, gx = w.gru[axis]
             a_x = conv.conv2d(shift_stack(motion, axis), gx, None)
             a_h = conv.conv2d(shift_stack(net, axis), gh, None)
             net = conv_gru(a_h, a_x, c[axis], net, lambda rh: conv.conv2d(shift_stack(rh, axis), gq, None))
-        delta_flow = conv.head_conv2d(conv.conv2d(net, *w.h1, padding=1, act="relu"), *w.h2, 1, 0, None)
-        mask = None
-        if upsample:
-            mask = conv.conv2d(conv.conv2d(net, *w.m1, padding=1, act="relu"), *w.m2)
+        delta_flow = self._flow_head(w, net)
+        mask = conv.conv2d(conv.conv2d(net, *w.m1, padding=1, act="relu"), *w.m2) if upsample else None
         return net, mask, delta_flow

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import DvsError, check
+from ._raft_host import gpu_arg
 from .raft import RAFT, SmallRAFT
 
 MAX_POINTS = 65536          # dvs_forward_interp is a brute-force search: h * w sources per image at the most
@@ -27,13 +28,8 @@ MAX_POINTS = 65536          # dvs_forward_interp is a brute-force search: h * w 
 
 def _flow_arg(who, flow, what):
     """A [2,h,w] or [N,2,h,w] fp32 GPU tensor as ([N,2,h,w] view, had a batch dimension)."""
-    if not torch.is_tensor(flow) or not flow.is_cuda:
-        raise DvsError("%s: GPU tensors only (got %s); this package has no CPU path" % (who, getattr(flow, "device", type(flow))))
-    if flow.dtype != torch.float32:
-        raise DvsError("%s: fp32 only, got %s" % (who, flow.dtype))
+    gpu_arg(who, flow, what + " expected", rank=(3, 4), ok=lambda shape: shape[-3] == 2 and min(shape) >= 1)
     batched = flow.dim() == 4
-    if flow.dim() not in (3, 4) or flow.shape[-3] != 2 or min(flow.shape) < 1:
-        raise DvsError("%s: %s expected, got %s" % (who, what, tuple(flow.shape)))
     return (flow if batched else flow[None]).detach(), batched
 
 
@@ -141,13 +137,7 @@ class FlowPredictor:
             raise DvsError("FlowPredictor: the model is in train() mode; call model.eval() (inference runs BatchNorm on its running "
                            "statistics and keeps no graph)")
         for name, t in (("image1", image1), ("image2", image2)):
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DvsError("FlowPredictor: %s: GPU tensors only (got %s); this package has no CPU path"
-                               % (name, getattr(t, "device", type(t))))
-            if t.dtype != torch.float32:
-                raise DvsError("FlowPredictor: %s: fp32 only, got %s" % (name, t.dtype))
-            if t.dim() != 4 or t.shape[1] != 3:
-                raise DvsError("FlowPredictor: %s: [B,3,H,W] expected, got %s" % (name, tuple(t.shape)))
+            gpu_arg("FlowPredictor: " + name, t, "[B,3,H,W] expected", ok=lambda shape: shape[1] == 3)
         if image1.shape != image2.shape or image1.device != image2.device:
             raise DvsError("FlowPredictor: image1 %s on %s, image2 %s on %s"
                            % (tuple(image1.shape), image1.device, tuple(image2.shape), image2.device))
