@@ -5,21 +5,7 @@ import weakref
 import torch
 
 from . import nn_ops
-from ._lib import DvsError
-
-CL = torch.channels_last
-
-
-def gpu_arg(who, t, want=None, rank=4, ok=None, no_cpu=DvsError, fp32_note=""):
-    """Refuse `t` unless it is a GPU tensor, fp32 and, where `want` ("[N,2,h,w] expected") says what is, of a rank in `rank` with
-    ok(t.shape).  Every message starts with `who`; `no_cpu` is the class raised for what is not on the GPU.  Reads is_cuda, dtype,
-    dim(), shape and device only, so a stand-in that has those passes as far as a tensor would."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise no_cpu("%s: GPU tensors only (got %s); this package has no CPU path" % (who, getattr(t, "device", type(t))))
-    if t.dtype != torch.float32:
-        raise DvsError("%s: fp32 only, got %s%s" % (who, t.dtype, fp32_note))
-    if want is not None and (t.dim() not in (rank if isinstance(rank, tuple) else (rank,)) or (ok is not None and not ok(t.shape))):
-        raise DvsError("%s: %s, got %s" % (who, want, tuple(t.shape)))
+from ._host import CL, aligned, gpu_arg                 # noqa: F401  (the family imports them from here)
 
 
 def _drop_on_gradient(owner_ref):

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import _lib, gradsink, zeropool
+from ._host import aligned
 from ._lib import check, ptr
 
 # DVS_BN_BWD_FUSED=1: reduce + apply without the partial-row sum kernel (dvs_bn_bwd).  Measured SLOWER over the step (26.96 -> 27.07 ms):
@@ -27,8 +28,9 @@ def _nn_generation_bump():
 
 
 def _cl(t):
-    """t in channels-last (NHWC) memory; a copy only when it is not there already."""
-    return t if t.is_contiguous(memory_format=CL) else t.contiguous(memory_format=CL)
+    """t in channels-last (NHWC) memory on a 16-byte boundary (the kernels read C/4 vectors); a copy only when it is not there
+    already."""
+    return aligned(t, CL)
 
 
 def _dp(t):

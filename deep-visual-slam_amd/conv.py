@@ -15,6 +15,7 @@ import weakref
 import torch
 
 from . import _lib, gradsink, zeropool
+from ._host import aligned
 from ._lib import ConvDesc, ConvFusion, check, ptr
 
 ACT = {None: 0, "none": 0, "relu": 1, "elu": 2, "sigmoid": 3, "gelu": 4}
@@ -28,10 +29,11 @@ def _has_grad(t):
 
 
 def _nhwc(t):
-    """Contiguous-NHWC requirement (a [B,1,H,W] or [B,C,1,1] tensor is both NCHW and NHWC)."""
+    """Contiguous-NHWC requirement (a [B,1,H,W] or [B,C,1,1] tensor is both NCHW and NHWC), on the 16-byte boundary the kernels'
+    vector loads assume: a dense tensor that starts elsewhere (a batch slice, a view at a storage offset) is copied."""
     if t.dtype != torch.float32:
         raise _lib.DvsError("fp32 tensors only (got %s)" % t.dtype)
-    return t if t.is_contiguous(memory_format=CL) else t.contiguous(memory_format=CL)
+    return aligned(t, CL)
 
 
 def _desc(B, Cin, H, W, w_shape, stride, pad, reflect):
@@ -52,7 +54,7 @@ UPSAMPLE_ONLY = "upsample-only"   # x2 marker: the logical input is upsample2x(x
 def _geometry(x, w_shape, x2, nchw_planar):
     """(x, x2, B, Cin, H, W) with layouts normalised for the kernels."""
     if nchw_planar:
-        x = x if x.is_contiguous() else x.contiguous()
+        x = aligned(x)
         B, Cin, H, W = x.shape
     else:
         x = _nhwc(x)

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, conv as _conv
+from ._host import aligned
 from ._lib import check, ptr
 
 CL = torch.channels_last
@@ -39,12 +40,23 @@ def _as_map(x2d):
 def gemm(x2d, w4d, bias=None, act=None, residual=None):
     """act(x2d [M,K] @ w^T + bias [+ residual [M,N]]) on the implicit-GEMM engine; w4d = weight as [N,K,1,1] (channels_last)."""
     M = x2d.shape[0]
-    res = _as_map(residual) if residual is not None else None
-    y = _conv.conv2d_forward(_as_map(x2d), w4d, bias, 1, 0, act=act, residual=res)
+    res = _as_map(aligned(residual)) if residual is not None else None
+    y = _conv.conv2d_forward(_as_map(aligned(x2d)), w4d, aligned(bias) if bias is not None else None, 1, 0, act=act, residual=res)
     return y.permute(0, 2, 3, 1).reshape(M, w4d.shape[0])
 
 
+def _own(who, **tensors):
+    """The inference helpers are handed what the model made itself: dense, 16-byte aligned tensors (csrc/vit.hip reads 16-byte
+    vectors and checks nothing).  Anything else is refused, not copied; the autograd Functions below copy."""
+    for name, t in tensors.items():
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            raise _lib.DvsError("%s: %s must be contiguous and 16-byte aligned (a model-internal helper: the training Functions "
+                                "accept any layout), got %s with strides %s at offset %d"
+                                % (who, name, tuple(t.shape), tuple(t.stride()), t.storage_offset()))
+
+
 def layernorm(x2d, weight, bias, eps):
+    _own("layernorm", x2d=x2d, weight=weight, bias=bias)
     y = torch.empty_like(x2d)
     check(_lib.lib().dvs_layernorm_fwd(ptr(x2d), ptr(weight), ptr(bias), ptr(y), x2d.shape[0], x2d.shape[1], eps, _lib.stream()),
           "dvs_layernorm_fwd")
@@ -52,6 +64,7 @@ def layernorm(x2d, weight, bias, eps):
 
 
 def attention(qkv2d, B, N, heads, head_dim):
+    _own("attention", qkv2d=qkv2d)
     out = torch.empty(B * N, heads * head_dim, device=qkv2d.device, dtype=torch.float32)
     check(_lib.lib().dvs_attention_fwd(ptr(qkv2d), ptr(out), None, B, N, heads, head_dim, head_dim ** -0.5, _lib.stream()), "dvs_attention_fwd")
     return out
@@ -60,7 +73,7 @@ def attention(qkv2d, B, N, heads, head_dim):
 def resize_bilinear_ac(x, H, W):
     """F.interpolate(x, (H, W), mode="bilinear", align_corners=True) on an NHWC-memory tensor."""
     B, C, h, w = x.shape
-    x = x if x.is_contiguous(memory_format=CL) else x.contiguous(memory_format=CL)
+    x = aligned(x, CL)
     y = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32, memory_format=CL)
     check(_lib.lib().dvs_resize_bilinear_ac(x.data_ptr(), y.data_ptr(), B, h, w, H, W, C, _lib.stream()), "dvs_resize_bilinear_ac")
     return y
@@ -69,7 +82,7 @@ def resize_bilinear_ac(x, H, W):
 def conv_transpose_s(x, w_gemm, bias_rep, k, cout):
     """nn.ConvTranspose2d(kernel_size=k, stride=k): one 1x1 GEMM to k*k*Cout channels, then the scatter."""
     B, _, h, w = x.shape
-    g = _conv.conv2d_forward(x, w_gemm, bias_rep, 1, 0)
+    g = _conv.conv2d_forward(x, w_gemm, aligned(bias_rep) if bias_rep is not None else None, 1, 0)
     y = torch.empty((B, cout, h * k, w * k), device=x.device, dtype=torch.float32, memory_format=CL)
     check(_lib.lib().dvs_deconv_shuffle(g.data_ptr(), y.data_ptr(), B, h, w, k, cout, _lib.stream()), "dvs_deconv_shuffle")
     return y
@@ -79,7 +92,7 @@ def conv_transpose_s(x, w_gemm, bias_rep, k, cout):
 class _AttentionF(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv2d, B, N, heads, head_dim):
-        qkv2d = qkv2d.contiguous()
+        qkv2d = aligned(qkv2d)
         out = torch.empty(B * N, heads * head_dim, device=qkv2d.device, dtype=torch.float32)
         lse = torch.empty(B, heads, N, device=qkv2d.device, dtype=torch.float32)
         check(_lib.lib().dvs_attention_fwd(ptr(qkv2d), ptr(out), ptr(lse), B, N, heads, head_dim, head_dim ** -0.5, _lib.stream()),
@@ -92,7 +105,7 @@ class _AttentionF(torch.autograd.Function):
     def backward(ctx, d_out):
         qkv2d, out, lse = ctx.saved_tensors
         B, N, heads, hd = ctx.dims
-        d_out = d_out.contiguous()
+        d_out = aligned(d_out)
         d_qkv = torch.empty_like(qkv2d)
         delta = torch.empty_like(lse)
         check(_lib.lib().dvs_attention_bwd(ptr(qkv2d), ptr(out), ptr(d_out), ptr(lse), ptr(delta), ptr(d_qkv), B, N, heads, hd,
@@ -103,8 +116,8 @@ class _AttentionF(torch.autograd.Function):
 class _LayerNormF(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2d, weight, bias, eps):
-        x2d = x2d.contiguous()
-        y = layernorm(x2d, weight.detach(), bias.detach(), eps)
+        x2d = aligned(x2d)
+        y = layernorm(x2d, aligned(weight.detach()), aligned(bias.detach()), eps)
         ctx.save_for_backward(x2d, weight)
         ctx.eps = eps
         return y
@@ -112,15 +125,20 @@ class _LayerNormF(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2d, weight = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = aligned(dy)
         dx = torch.empty_like(x2d)
         dg, db = torch.zeros_like(weight), torch.zeros_like(weight)
-        check(_lib.lib().dvs_layernorm_bwd(ptr(x2d), ptr(weight.detach().contiguous()), ptr(dy), ptr(dx), ptr(dg), ptr(db), x2d.shape[0],
+        check(_lib.lib().dvs_layernorm_bwd(ptr(x2d), ptr(aligned(weight.detach())), ptr(dy), ptr(dx), ptr(dg), ptr(db), x2d.shape[0],
                                            x2d.shape[1], ctx.eps, _lib.stream()), "dvs_layernorm_bwd")
         return dx, dg, db, None
 
 
 _ACT_CODE = {"relu": 1, "gelu": 4}
+
+
+def _dense_format(x):
+    """The memory format in which x is dense (channels_last where it is that and not planar), else the planar one."""
+    return CL if x.dim() == 4 and x.is_contiguous(memory_format=CL) and not x.is_contiguous() else torch.contiguous_format
 
 
 class _ActF(torch.autograd.Function):
@@ -130,7 +148,7 @@ class _ActF(torch.autograd.Function):
     def forward(ctx, x, act):
         if x.numel() % 4:
             raise _lib.DvsError("activation: element count must be a multiple of 4")
-        dense = x if (x.is_contiguous() or x.is_contiguous(memory_format=CL)) else x.contiguous()
+        dense = aligned(x, _dense_format(x))
         y = torch.empty_like(dense)
         check(_lib.lib().dvs_act_fwd(dense.data_ptr(), y.data_ptr(), dense.numel(), _ACT_CODE[act], _lib.stream()), "dvs_act_fwd")
         ctx.save_for_backward(dense)
@@ -140,8 +158,7 @@ class _ActF(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        if dy.stride() != x.stride():
-            dy = dy.contiguous(memory_format=CL) if x.dim() == 4 and x.is_contiguous(memory_format=CL) and not x.is_contiguous() else dy.contiguous()
+        dy = aligned(dy, _dense_format(x))
         dx = torch.empty_like(x)
         check(_lib.lib().dvs_act_bwd_in(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), _ACT_CODE[ctx.act], _lib.stream()), "dvs_act_bwd_in")
         return dx, None
@@ -157,7 +174,7 @@ class _ResizeF(torch.autograd.Function):
     def backward(ctx, dy):
         B, C, H, W = dy.shape
         h, w = ctx.in_hw
-        dy = dy if dy.is_contiguous(memory_format=CL) else dy.contiguous(memory_format=CL)
+        dy = aligned(dy, CL)
         dx = torch.empty((B, C, h, w), device=dy.device, dtype=torch.float32, memory_format=CL)
         check(_lib.lib().dvs_resize_bilinear_ac_bwd(dy.data_ptr(), dx.data_ptr(), B, h, w, H, W, C, _lib.stream()), "dvs_resize_bilinear_ac_bwd")
         return dx, None, None
@@ -169,7 +186,7 @@ class _ShuffleF(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, k, cout):
         B, _, h, w = g.shape
-        g = g if g.is_contiguous(memory_format=CL) else g.contiguous(memory_format=CL)
+        g = aligned(g, CL)
         y = torch.empty((B, cout, h * k, w * k), device=g.device, dtype=torch.float32, memory_format=CL)
         check(_lib.lib().dvs_deconv_shuffle(g.data_ptr(), y.data_ptr(), B, h, w, k, cout, _lib.stream()), "dvs_deconv_shuffle")
         ctx.dims = (B, h, w, k, cout)
@@ -178,7 +195,7 @@ class _ShuffleF(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         B, h, w, k, cout = ctx.dims
-        dy = dy if dy.is_contiguous(memory_format=CL) else dy.contiguous(memory_format=CL)
+        dy = aligned(dy, CL)
         dg = torch.empty((B, k * k * cout, h, w), device=dy.device, dtype=torch.float32, memory_format=CL)
         check(_lib.lib().dvs_deconv_unshuffle(dy.data_ptr(), dg.data_ptr(), B, h, w, k, cout, _lib.stream()), "dvs_deconv_unshuffle")
         return dg, None, None
@@ -188,7 +205,7 @@ def linear_train(x2d, weight, bias):
     """x2d @ weight^T + bias with autograd, on the implicit-GEMM engine's forward / data-gradient / weight-gradient kernels
     (a Linear is a 1x1 convolution of the [1, K, 1, M] token map)."""
     N, K = weight.shape
-    y = _conv.conv2d(_as_map(x2d.contiguous()), weight.reshape(N, K, 1, 1), bias, 1, 0, 0, None)
+    y = _conv.conv2d(_as_map(aligned(x2d)), weight.reshape(N, K, 1, 1), aligned(bias) if bias is not None else None, 1, 0, 0, None)
     return y.permute(0, 2, 3, 1).reshape(x2d.shape[0], N)
 
 

@@ -286,6 +286,12 @@ class FusedAdam(torch.optim.Optimizer):
     as in torch, no state because they never receive a gradient); default = the arena's own order."""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, params=None):
+        for name in ("params", "grads"):
+            t = getattr(flat, name)
+            if t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+                raise _lib.DvsError("FusedAdam: the arena's %s are written in place and must be one contiguous, 16-byte aligned fp32 "
+                                    "vector (dp.FlatParams makes it), got %s %s with strides %s"
+                                    % (name, t.dtype, tuple(t.shape), tuple(t.stride())))
         self.flat = flat
         self._slot = {id(p): i for i, p in enumerate(flat.tensors)}
         plist = list(params) if params is not None else list(flat.tensors)

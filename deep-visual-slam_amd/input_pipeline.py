@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import aligned
 from ._lib import check, ptr
 
 
@@ -107,12 +108,16 @@ def u8_to_f32_planar(frames_u8, bgr=False, out=None):
     """[N,H,W,3] uint8 -> [N,3,H,W] fp32 in [0,1] (ToTensor; bgr=True also swaps to RGB)."""
     if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
         raise _lib.DvsError("u8_to_f32_planar: uint8 GPU tensor expected (got %s on %s)" % (frames_u8.dtype, frames_u8.device))
-    frames_u8 = frames_u8.contiguous()
+    frames_u8 = aligned(frames_u8, bytes=4)             # the kernel reads four bytes at a time
     N, H, W, ch = frames_u8.shape
     if ch != 3:
         raise _lib.DvsError("u8_to_f32_planar: [N,H,W,3] expected")
     if out is None:
         out = torch.empty(N, 3, H, W, device=frames_u8.device, dtype=torch.float32)
+    elif (tuple(out.shape) != (N, 3, H, W) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous()
+          or out.data_ptr() % 16):
+        raise _lib.DvsError("u8_to_f32_planar: out is written in place and must be a contiguous, 16-byte aligned fp32 GPU tensor "
+                            "[%d,3,%d,%d], got %s %s with strides %s" % (N, H, W, out.dtype, tuple(out.shape), tuple(out.stride())))
     check(_lib.lib().dvs_u8_to_f32_planar(ptr(frames_u8), ptr(out), N, H, W, int(bool(bgr)), _lib.stream()), "dvs_u8_to_f32_planar")
     return out
 

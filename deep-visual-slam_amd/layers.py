@@ -66,7 +66,8 @@ class ConvBlock(nn.Module):
 
 
 class BackprojectDepth(nn.Module):
-    """Layer to transform a depth image into a point cloud (model/layers.py:139-168)."""
+    """Layer to transform a depth image into a point cloud (model/layers.py:139-168).  inv_K is [B,4,4], or [1,4,4] handed to
+    every image of the batch as the reference's matmul broadcasts it; any other shape is refused."""
 
     def __init__(self, batch_size, height, width):
         super().__init__()
@@ -78,7 +79,8 @@ class BackprojectDepth(nn.Module):
 
 class Project3D(nn.Module):
     """Layer which projects 3D points into a camera with intrinsics K and at position T
-    (model/layers.py:171-193)."""
+    (model/layers.py:171-193).  points is [B,4,height*width]; K and T are [B,4,4], or [1,4,4] handed to every image of the batch
+    as the reference's matmul broadcasts it; any other shape is refused."""
 
     def __init__(self, batch_size, height, width, eps=1e-7):
         super().__init__()

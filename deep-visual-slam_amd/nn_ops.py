@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from . import conv as _conv
+from ._host import aligned
 
 CL = torch.channels_last
 
@@ -51,6 +52,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, reflect_pad=0, act=None, x
     passthrough: returns (y, x') -- x' is x, on the training path as a second output of this convolution's autograd node, so
     that the gradient of x's NEXT consumer is added inside this convolution's data-gradient kernel."""
     _require_gpu(x, "conv2d")
+    if bias is not None:
+        bias = aligned(bias)                    # x, x2 and the weight are normalised by conv._nhwc
     planar = planar_norm is not None
     if passthrough and not (_PASSTHROUGH and torch.is_grad_enabled() and x.requires_grad and not _lib.deterministic()
                             and x2 is None and not upsample and not planar):
@@ -272,7 +275,7 @@ class _MaxPool3x3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, passthrough=False):
         x_in = x
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = aligned(x, torch.channels_last)
         B, C, H, W = x.shape
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
@@ -293,9 +296,9 @@ class _MaxPool3x3s2(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         B, C, H, W = ctx.shape
         cl = torch.channels_last
-        dy = dy if dy.is_contiguous(memory_format=cl) else dy.contiguous(memory_format=cl)
+        dy = aligned(dy, cl)
         if dxa is not None:
-            dxa = dxa if dxa.is_contiguous(memory_format=cl) else dxa.contiguous(memory_format=cl)
+            dxa = aligned(dxa, cl)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=torch.float32, memory_format=cl)
         _lib.check(_lib.lib().dvs_maxpool3x3s2_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(),
                                                    dxa.data_ptr() if dxa is not None else None, B, H, W, C, _lib.stream()),
@@ -319,7 +322,7 @@ class _Upsample2x(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        x = x if x.is_contiguous(memory_format=CL) else x.contiguous(memory_format=CL)
+        x = aligned(x, CL)
         B, C, H, W = x.shape
         y = torch.empty((B, C, 2 * H, 2 * W), device=x.device, dtype=torch.float32, memory_format=CL)
         _lib.check(_lib.lib().dvs_upsample2x_fwd(x.data_ptr(), y.data_ptr(), B, H, W, C, _lib.stream()), "dvs_upsample2x_fwd")
@@ -329,7 +332,7 @@ class _Upsample2x(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         B, C, H, W = ctx.shape
-        dy = dy if dy.is_contiguous(memory_format=CL) else dy.contiguous(memory_format=CL)
+        dy = aligned(dy, CL)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=torch.float32, memory_format=CL)
         _lib.check(_lib.lib().dvs_upsample2x_bwd(dy.data_ptr(), dx.data_ptr(), B, H, W, C, _lib.stream()), "dvs_upsample2x_bwd")
         return dx

@@ -6,6 +6,7 @@ import os
 import torch
 
 from . import _lib
+from ._host import gpu_arg, shaped
 from ._lib import ChainBwdIO, ChainCfg, ChainFwdIO, check, ptr
 
 MAX_SCALES = _lib.MAX_SCALES
@@ -47,7 +48,14 @@ class _PoseToMat(torch.autograd.Function):
 
 
 def pose_to_mat(axisangle, translation, invert=False):
-    """transformation_from_parameters (vo/learner_func.py:29-46) on the GPU."""
+    """transformation_from_parameters (vo/learner_func.py:29-46) on the GPU: both arguments are read as rows of 3."""
+    gpu_arg("pose_to_mat: axisangle", axisangle)
+    gpu_arg("pose_to_mat: translation", translation)
+    if axisangle.numel() % 3 or translation.numel() % 3 or axisangle.numel() != translation.numel() or axisangle.numel() == 0:
+        raise _lib.DvsError("pose_to_mat: translation must hold as many rows of 3 as axisangle %s, got %s"
+                            % (tuple(axisangle.shape), tuple(translation.shape)))
+    if translation.device != axisangle.device:
+        raise _lib.DvsError("pose_to_mat: translation is on %s, not on %s" % (translation.device, axisangle.device))
     return _PoseToMat.apply(axisangle, translation, invert)
 
 
@@ -202,6 +210,27 @@ def loss_chain(target, src_l, src_r, K, inv_K, T_l, T_r, disps, noise=None, seed
                auto_mask=True, min_depth=0.1, max_depth=10.0, ssim_ratio=0.85, smoothness_ratio=1e-3, aux_stream=None):
     """Fused view-synthesis loss chain.  Returns (losses[S], sel[B,H,W] uint8, extras) where extras is a
     per-scale list of dicts {disp_up, depth, grid:(l,r), color:(l,r)} when materialize=True, else []."""
+    gpu_arg("loss_chain: target", target, "[B,3,H,W] expected", ok=lambda s: s[1] == 3 and min(s) >= 1)
+    B, _, H, W = target.shape
+    for name, t in (("src_l", src_l), ("src_r", src_r)):
+        gpu_arg("loss_chain: " + name, t)
+        shaped("loss_chain", name, t, "[B,3,H,W] like target", (B, 3, H, W), like=target)
+    for name, t in (("K", K), ("inv_K", inv_K), ("T_l", T_l), ("T_r", T_r)):
+        gpu_arg("loss_chain: " + name, t)
+        shaped("loss_chain", name, t, "[B,4,4] for target %s" % (tuple(target.shape),), (B, 4, 4), like=target)
+    disps = list(disps)
+    if not 1 <= len(disps) <= MAX_SCALES:
+        raise _lib.DvsError("loss_chain: 1 .. %d disparity scales, got %d" % (MAX_SCALES, len(disps)))
+    for s, d in enumerate(disps):
+        name = "disps[%d]" % s
+        gpu_arg("loss_chain: " + name, d, "[B,1,h,w] for target %s expected" % (tuple(target.shape),),
+                ok=lambda sh: sh[0] == B and sh[1] == 1 and min(sh) >= 1)
+        if d.device != target.device:
+            raise _lib.DvsError("loss_chain: %s is on %s, not on %s" % (name, d.device, target.device))
+    if noise is not None:
+        gpu_arg("loss_chain: noise", noise)
+        shaped("loss_chain", "noise", noise, "[S,B,2,H,W] for target %s" % (tuple(target.shape),), (len(disps), B, 2, H, W),
+               like=target)
     opts = dict(auto_mask=auto_mask, min_depth=min_depth, max_depth=max_depth, ssim_ratio=ssim_ratio,
                 smoothness_ratio=smoothness_ratio, seed=seed, materialize=materialize, aux_stream=aux_stream)
     # the backward may hand d disp_1.. and d T out before they are complete (computed on a second stream) only if their
@@ -245,7 +274,17 @@ class _Backproject(torch.autograd.Function):
         return d_depth, None
 
 
+def _per_image_4x4(op, name, m, B, like):
+    """A [B,4,4] matrix stack, or [1,4,4] handed to every image as the reference's matmul broadcasts it."""
+    gpu_arg("%s: %s" % (op, name), m)
+    shaped(op, name, m, "[B,4,4] or [1,4,4] for %s" % (tuple(like.shape),), (B, 4, 4), (1, 4, 4), like=like)
+    return m.expand(B, 4, 4)
+
+
 def backproject(depth, inv_K):
+    """BackprojectDepth (model/layers.py:139-168): depth [B,1,H,W], inv_K [B,4,4] or [1,4,4] -> camera points [B,4,H*W]."""
+    gpu_arg("backproject: depth", depth, "[B,1,H,W] expected", ok=lambda s: s[1] == 1 and min(s) >= 1)
+    inv_K = _per_image_4x4("backproject", "inv_K", inv_K, depth.shape[0], depth)
     return _Backproject.apply(depth, inv_K)
 
 
@@ -275,6 +314,12 @@ class _Project(torch.autograd.Function):
 
 
 def project(points, K, T, H, W, eps=1e-7):
+    """Project3D (model/layers.py:171-193): points [B,4,H*W], K and T [B,4,4] or [1,4,4] -> sampling grid [B,H,W,2]."""
+    H, W = int(H), int(W)
+    gpu_arg("project: points", points, "[B,4,H*W] with H=%d, W=%d expected" % (H, W), rank=3,
+            ok=lambda s: s[0] >= 1 and s[1] == 4 and s[2] == H * W and H >= 1 and W >= 1)
+    K = _per_image_4x4("project", "K", K, points.shape[0], points)
+    T = _per_image_4x4("project", "T", T, points.shape[0], points)
     return _Project.apply(points, K, T, H, W, eps)
 
 
@@ -300,6 +345,10 @@ class _SSIM(torch.autograd.Function):
 
 
 def ssim(x, y):
+    """SSIM (model/layers.py:218-248) of two [B,C,H,W] images of one shape (the 3x3 reflection-padded windows need H, W >= 2)."""
+    gpu_arg("ssim: x", x, "[B,C,H,W] with H, W >= 2 expected", ok=lambda s: min(s[:2]) >= 1 and min(s[2:]) >= 2)
+    gpu_arg("ssim: y", y)
+    shaped("ssim", "y", y, "x's shape", tuple(x.shape), like=x)
     return _SSIM.apply(x, y)
 
 
@@ -329,6 +378,13 @@ class _Smooth(torch.autograd.Function):
 
 
 def smooth_loss(disp, img):
+    """get_smooth_loss (model/layers.py:202-215): disp [B,1,H,W], img [B,C,H,W] of the same B, H, W -> a scalar."""
+    gpu_arg("smooth_loss: disp", disp, "[B,1,H,W] expected", ok=lambda s: s[1] == 1 and min(s) >= 1)
+    B, _, H, W = disp.shape
+    gpu_arg("smooth_loss: img", img, "[B,C,H,W] of disp's B, H, W %s expected" % (tuple(disp.shape),),
+            ok=lambda s: (s[0], s[2], s[3]) == (B, H, W) and s[1] >= 1)
+    if img.device != disp.device:
+        raise _lib.DvsError("smooth_loss: img is on %s, not on %s" % (img.device, disp.device))
     return _Smooth.apply(disp, img)
 
 
@@ -380,7 +436,25 @@ class _DepthLoss(torch.autograd.Function):
 
 
 def depth_multiscale_losses(pred_depths, gt_depth, rgb, valid_mask, variance_focus=0.85):
-    """(silog [S], smooth [S]) of the upsampled per-scale depth predictions (depth/depth_learner.py:97-117)."""
+    """(silog [S], smooth [S]) of the upsampled per-scale depth predictions (depth/depth_learner.py:97-117): pred_depths[s]
+    [B,1,h,w], gt_depth and valid_mask [B,1,H,W] or [B,H,W], rgb [B,3,H,W]."""
+    op = "depth_multiscale_losses"
+    gpu_arg(op + ": rgb", rgb, "[B,3,H,W] expected", ok=lambda s: s[1] == 3 and min(s) >= 1)
+    B, _, H, W = rgb.shape
+    gpu_arg(op + ": gt_depth", gt_depth)
+    if not torch.is_tensor(valid_mask) or not valid_mask.is_cuda:
+        raise _lib.DvsError("%s: valid_mask: GPU tensors only (got %s); this package has no CPU path"
+                            % (op, getattr(valid_mask, "device", type(valid_mask))))
+    for name, t in (("gt_depth", gt_depth), ("valid_mask", valid_mask)):
+        shaped(op, name, t, "[B,1,H,W] or [B,H,W] for rgb %s" % (tuple(rgb.shape),), (B, 1, H, W), (B, H, W), like=rgb)
+    pred_depths = list(pred_depths)
+    if not 1 <= len(pred_depths) <= MAX_SCALES:
+        raise _lib.DvsError("%s: 1 .. %d scales, got %d" % (op, MAX_SCALES, len(pred_depths)))
+    for s, d in enumerate(pred_depths):
+        gpu_arg("%s: pred_depths[%d]" % (op, s), d, "[B,1,h,w] for rgb %s expected" % (tuple(rgb.shape),),
+                ok=lambda sh: sh[0] == B and sh[1] == 1 and min(sh) >= 1)
+        if d.device != rgb.device:
+            raise _lib.DvsError("%s: pred_depths[%d] is on %s, not on %s" % (op, s, d.device, rgb.device))
     out = _DepthLoss.apply(gt_depth, valid_mask, rgb, float(variance_focus), *pred_depths)
     S = len(pred_depths)
     return out[:S], out[S:]

@@ -71,6 +71,10 @@ def depth_to_cloud(depth_or_disp, image, K, M=None, *, from_disp=None, stride=1,
         raise DvsError("depth_to_cloud: K must be [B,3,3] or [B,4,4], got %s" % (tuple(K.shape),))
     if M is not None and tuple(M.shape) != (B, 4, 4):
         raise DvsError("depth_to_cloud: M must be [B,4,4], got %s" % (tuple(M.shape),))
+    for name, t in (("out", out), ("count", count), ("index", index), ("workspace", workspace)):
+        if t is not None and not t.is_contiguous():
+            raise DvsError("depth_to_cloud: %s is written in place and must be contiguous, got %s with strides %s"
+                           % (name, tuple(t.shape), tuple(t.stride())))
     cfg = make_cfg(B, H, W, stride, from_disp, z_range, K.shape[1])
     n_max = capacity(cfg)
     dev = depth_or_disp.device
@@ -131,6 +135,10 @@ class PoseChain:
         M = new(B, 4, 4) if M is None else M
         tq = new(B, 7) if tq is None else tq
         world = self.world if world is None else world
+        for name, t, shape in (("poses", poses, (B, 4, 4)), ("M", M, (B, 4, 4)), ("tq", tq, (B, 7)), ("world", world, (4, 4))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise DvsError("PoseChain.step: %s is written in place and must be a contiguous fp32 GPU tensor %s, got %s %s "
+                               "with strides %s" % (name, list(shape), t.dtype, tuple(t.shape), tuple(t.stride())))
         check(_lib.lib().dvs_pose_chain(ptr(T), ptr(self.left), ptr(world), ptr(poses), ptr(M), ptr(tq), B, _lib.stream()),
               "dvs_pose_chain")
         return poses, M, tq

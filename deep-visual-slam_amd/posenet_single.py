@@ -18,9 +18,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, nn_ops
-from . import conv as _conv
 from ._lib import DvsError, check
-from ._raft_host import gpu_arg
+from ._raft_host import CL, aligned, gpu_arg
 from .raft import SmallRAFT
 from .resnet_encoder import ResnetEncoder
 
@@ -73,19 +72,13 @@ def pool_fc_slice_pixels():
     return int(_lib.lib().dvs_pool_fc_slice_pixels())
 
 
-def _aligned(t):
-    """t, contiguous and on a 16-byte boundary as the entries demand: a row slice of a larger tensor (rows of 6 floats) is copied."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 class _PoolFc(torch.autograd.Function):
     """scale * fc(mean_hw(relu(y))) on dvs_pool_fc_fwd / dvs_pool_fc_bwd (csrc/posehead.hip); y is read in NHWC memory."""
 
     @staticmethod
     def forward(ctx, y, weight, bias, relu, scale):
-        y = _conv._nhwc(y.detach())
-        weight, bias = _aligned(weight.detach()), _aligned(bias.detach()) if bias is not None else None
+        y = aligned(y.detach(), CL)
+        weight, bias = aligned(weight.detach()), aligned(bias.detach()) if bias is not None else None
         N, Cn, H, W = y.shape
         J, P = weight.shape[0], H * W
         lib = _lib.lib()
@@ -108,7 +101,7 @@ class _PoolFc(torch.autograd.Function):
         relu, scale, has_bias = ctx.head
         N, Cn, H, W = y.shape
         J = weight.shape[0]
-        dout = _aligned(dout)
+        dout = aligned(dout)
         dy = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32)
         dw = torch.empty((J, Cn), device=y.device, dtype=torch.float32)
         db = torch.empty((J,), device=y.device, dtype=torch.float32) if has_bias else None

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import _lib, conv
 from ._lib import DvsError, check
-from ._raft_host import CL, gpu_arg
+from ._raft_host import CL, aligned, gpu_arg
 from .raft_corr import AlternateCorrBlock, CorrBlock
 from .raft_encoder import BasicEncoder, SmallEncoder
 from .raft_update import BasicUpdateBlock, SmallUpdateBlock
@@ -27,10 +27,8 @@ from .raft_update import BasicUpdateBlock, SmallUpdateBlock
 def _flow_layout(t):
     """(tensor whose memory the kernels read in place, planar flag) of a [N,2,h,w] tensor."""
     if t.is_contiguous():
-        return t, 1
-    if not t.is_contiguous(memory_format=CL):
-        t = t.contiguous(memory_format=CL)
-    return t, 0
+        return aligned(t), 1
+    return aligned(t, CL), 0
 
 
 def _is_flow(shape):
@@ -50,7 +48,7 @@ class _Upflow8(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         N, h, w, nchw = ctx.geometry
-        dout = dout.contiguous()
+        dout = aligned(dout)
         if nchw:
             dflow = torch.empty((N, 2, h, w), device=dout.device, dtype=torch.float32)
         else:
@@ -83,7 +81,7 @@ def _option(args, name, default):
 class _ConvexUp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, mask, mask_scale):
-        flow, mask = flow.detach().contiguous(), conv._nhwc(mask.detach())
+        flow, mask = aligned(flow.detach()), aligned(mask.detach(), CL)
         N, _, h, w = flow.shape
         out = torch.empty((N, 2, 8 * h, 8 * w), device=flow.device, dtype=torch.float32)
         check(_lib.lib().dvs_convex_up_fwd(flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, h, w, mask_scale, _lib.stream()),
@@ -99,7 +97,7 @@ class _ConvexUp(torch.autograd.Function):
         need_flow, need_mask = ctx.needs_input_grad[:2]
         if not (need_flow or need_mask):
             return None, None, None
-        dout = dout.contiguous()
+        dout = aligned(dout)
         dflow = ws = dmask = None
         nbytes = 0
         if need_flow:                                       # the workspace and the gather kernel serve dflow alone

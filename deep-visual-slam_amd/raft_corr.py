@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import CorrCfg, DvsError, check, ptr
-from ._raft_host import CL, gpu_arg
+from ._raft_host import CL, aligned, gpu_arg
 
 
 def _cfg(B, Cn, H, W, num_levels, radius, nchw1=0, nchw2=0):
@@ -61,9 +61,9 @@ def _sizes(cfg):
 def _layout(t):
     """(tensor whose memory the kernels read in place, nchw flag): channels_last memory is position-major already."""
     if t.is_contiguous(memory_format=CL):
-        return t.permute(0, 2, 3, 1), 0
+        return aligned(t, CL).permute(0, 2, 3, 1), 0
     if t.is_contiguous():
-        return t, 1
+        return aligned(t), 1
     return t.contiguous(memory_format=CL).permute(0, 2, 3, 1), 0
 
 
@@ -137,7 +137,7 @@ class _Lookup(torch.autograd.Function):
         st = ctx.state
         cfg = st.cfg
         nhwc = int(dout.is_contiguous(memory_format=CL) and not dout.is_contiguous())
-        dout = dout.permute(0, 2, 3, 1) if nhwc else dout.contiguous()
+        dout = dout.permute(0, 2, 3, 1) if nhwc else aligned(dout, bytes=4)      # the lookups read single floats
         check(_lib.lib().dvs_corr_lookup_bwd(C.byref(cfg), ptr(ctx.coords), ptr(dout), nhwc, ptr(st.grad_pyramid()), _lib.stream()),
               "dvs_corr_lookup_bwd")
         return torch.zeros(1, device=dout.device, dtype=torch.float32), None, None, None
@@ -163,7 +163,7 @@ def _check_coords(name, coords, cfg, device):
                        "(coords1 = coords1.detach()); pass coords.detach()" % name)
     if tuple(coords.shape) != (cfg.B, 2, cfg.H, cfg.W):
         raise DvsError("%s: coords must be [%d,2,%d,%d], got %s" % (name, cfg.B, cfg.H, cfg.W, tuple(coords.shape)))
-    return coords.contiguous()
+    return aligned(coords, bytes=4)
 
 
 def _memory_format_flag(memory_format):
@@ -286,7 +286,7 @@ class _AltLookup(torch.autograd.Function):
         cfg = st.cfg
         _, _, pooled = ctx.saved_tensors                # (reading them is what checks their versions)
         nhwc = int(dout.is_contiguous(memory_format=CL) and not dout.is_contiguous())
-        dout = dout.permute(0, 2, 3, 1) if nhwc else dout.contiguous()
+        dout = dout.permute(0, 2, 3, 1) if nhwc else aligned(dout, bytes=4)      # the lookups read single floats
         N = cfg.H * cfg.W
         d1 = torch.empty(cfg.B, N, cfg.C, device=dout.device, dtype=torch.float32)
         d2 = torch.zeros(cfg.B, N, cfg.C, device=dout.device, dtype=torch.float32)

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from . import _lib, conv
 from . import bn as _bn_ops
 from ._lib import DvsError, check
-from ._raft_host import CL, DerivedOperands, gpu_arg
+from ._raft_host import CL, DerivedOperands, aligned, gpu_arg
 
 
 def slice_pixels():
@@ -45,9 +45,9 @@ def _workspace(N, HW, Cn, device):
 class _InormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, residual, norm, relu):
-        y = conv._nhwc(y.detach())
+        y = aligned(y.detach(), CL)
         N, Cn, H, W = y.shape
-        res = conv._nhwc(residual.detach()) if residual is not None else None
+        res = aligned(residual.detach(), CL) if residual is not None else None
         out = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32)
         table = ws = None
         nbytes = 0
@@ -66,7 +66,7 @@ class _InormAct(torch.autograd.Function):
         y, out, table = ctx.saved_tensors
         norm, relu = ctx.flags
         N, Cn, H, W = y.shape
-        dout = conv._nhwc(dout)
+        dout = aligned(dout, CL)
         dy = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32)
         dres = torch.empty((N, H, W, Cn), device=y.device, dtype=torch.float32) if out is not None else None
         ws, nbytes = _workspace(N, H * W, Cn, y.device) if norm else (None, 0)

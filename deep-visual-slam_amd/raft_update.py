@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib, conv
 from ._lib import DvsError, check
-from ._raft_host import CL, DerivedOperands, gpu_arg
+from ._raft_host import CL, DerivedOperands, aligned, gpu_arg
 
 CTX_DIM = 64            # channels of `inp` (SmallRAFT's context_dim, raft.py:34)
 MOTION_DIM = 82         # SmallMotionEncoder's 80 + the 2 flow channels (update.py:77)
@@ -87,7 +87,7 @@ class _Gates(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a_h, a_x, c, h, link):
         ctx.set_materialize_grads(False)
-        a_h, a_x, c, h = (conv._nhwc(t.detach()) for t in (a_h, a_x, c, h))
+        a_h, a_x, c, h = (aligned(t.detach(), CL) for t in (a_h, a_x, c, h))
         z, r, rh = _gates_raw(a_h, a_x, c, h)
         ctx.save_for_backward(r, h)
         ctx.link = link
@@ -108,7 +108,7 @@ class _Gates(torch.autograd.Function):
         r, h = ctx.saved_tensors
         P, hd = _rows(h)
         # a conv_q that hands no gradient back for r * h: the z and q columns the blend node wrote still count
-        d_rh = torch.zeros_like(h) if d_rh is None else conv._nhwc(d_rh)
+        d_rh = torch.zeros_like(h) if d_rh is None else aligned(d_rh, CL)
         dh = _empty_map(h, hd)
         check(_lib.lib().dvs_gru_gates_bwd(d_rh.data_ptr(), h.data_ptr(), r.data_ptr(), dh_a.data_ptr(), dpre.data_ptr(),
                                            dah.data_ptr(), dh.data_ptr(), P, hd, _lib.stream()), "dvs_gru_gates_bwd")
@@ -121,7 +121,7 @@ class _Gates(torch.autograd.Function):
 class _Blend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a_q, a_x, c, z, h, link):
-        a_q, a_x, c, z, h = (conv._nhwc(t.detach()) for t in (a_q, a_x, c, z, h))
+        a_q, a_x, c, z, h = (aligned(t.detach(), CL) for t in (a_q, a_x, c, z, h))
         q, h_new = _blend_raw(a_q, a_x, c, z, h)
         ctx.save_for_backward(z, q, h)
         ctx.link = link
@@ -131,7 +131,7 @@ class _Blend(torch.autograd.Function):
     def backward(ctx, g):
         z, q, h = ctx.saved_tensors
         P, hd = _rows(h)
-        g = conv._nhwc(g)
+        g = aligned(g, CL)
         dpre, dah, dq, dh_a = _empty_map(h, 3 * hd), _empty_map(h, 2 * hd), _empty_map(h, hd), _empty_map(h, hd)
         check(_lib.lib().dvs_gru_blend_bwd(g.data_ptr(), z.data_ptr(), q.data_ptr(), h.data_ptr(), dpre.data_ptr(), dah.data_ptr(),
                                            dq.data_ptr(), dh_a.data_ptr(), P, hd, _lib.stream()), "dvs_gru_blend_bwd")
@@ -145,11 +145,11 @@ def conv_gru(a_h, a_x, c, h, conv_q):
     """h' of the split ConvGRU from the three pre-activation parts; conv_q(r * h) is the caller's convolution of the reset
     hidden state.  Differentiable in a_h, a_x, c, h and whatever conv_q closes over."""
     if not torch.is_grad_enabled() or not any(t.requires_grad for t in (a_h, a_x, c, h)):
-        a_h, a_x, c, h = (conv._nhwc(t) for t in (a_h, a_x, c, h))
+        a_h, a_x, c, h = (aligned(t, CL) for t in (a_h, a_x, c, h))
         z, _, rh = _gates_raw(a_h, a_x, c, h)
         a_q = conv_q(rh)
         if not a_q.requires_grad:
-            return _blend_raw(conv._nhwc(a_q), a_x, c, z, h)[1]
+            return _blend_raw(aligned(a_q, CL), a_x, c, z, h)[1]
         return _Blend.apply(a_q, a_x, c, z, h, _Link())
     link = _Link()
     z, _, rh = _Gates.apply(a_h, a_x, c, h, link)
@@ -323,7 +323,7 @@ class SmallUpdateBlock(_UpdateBlock):
 class _ShiftStack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, axis):
-        x = conv._nhwc(x.detach())
+        x = aligned(x.detach(), CL)
         B, Cn, H, W = x.shape
         out = torch.empty((B, H, W, 5 * Cn), device=x.device, dtype=torch.float32)
         check(_lib.lib().dvs_shift_stack_fwd(x.data_ptr(), out.data_ptr(), B, H, W, Cn, axis, _lib.stream()), "dvs_shift_stack_fwd")
@@ -333,7 +333,7 @@ class _ShiftStack(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         B, Cn, H, W, axis = ctx.geometry
-        g = conv._nhwc(g)
+        g = aligned(g, CL)
         dx = torch.empty((B, H, W, Cn), device=g.device, dtype=torch.float32)
         check(_lib.lib().dvs_shift_stack_bwd(g.data_ptr(), dx.data_ptr(), B, H, W, Cn, axis, _lib.stream()), "dvs_shift_stack_bwd")
         return dx.permute(0, 3, 1, 2), None

@@ -14,6 +14,10 @@ from conftest import golden_chain_inputs, load_golden
 pytestmark = pytest.mark.gpu
 
 
+LOSS_TOL = (1e-7, 1e-5)                     # (atol, rtol) of a loss scalar
+GRAD_TOL = dict(atol=2e-8, rtol=2e-3)       # close_frac's, of a disparity gradient
+
+
 def close(a, b, atol, rtol):
     a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
     b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
@@ -67,14 +71,14 @@ def test_chain_vs_reference_golden(gpu_device, name):
         cm, cp = rec["meta/clamped_m1"], rec["meta/clamped_p1"]
         assert cm[0] >= 0.1 and cm[2] >= 0.1 and cp[1] >= 0.1 and cp[3] >= 0.1
     out = run_chain(gpu_device, sample, disps, poses, noise, ns)
-    close(out["total"], rec["loss"], 1e-7, 1e-5)
+    close(out["total"], rec["loss"], *LOSS_TOL)
     close(out["T"][0], rec["out/T_m1"], 2e-6, 2e-5)
     close(out["T"][1], rec["out/T_p1"], 2e-6, 2e-5)
     for s in range(ns):
-        close(out["losses"][s], rec["loss/%d" % s], 1e-7, 1e-5)
+        close(out["losses"][s], rec["loss/%d" % s], *LOSS_TOL)
         sel = ((out["sel"].cpu().numpy() >> (2 * s)) & 3) > 1
         assert (sel[:, None] != rec["out/identity_selection%d" % s].astype(bool)).mean() < 1e-3
-        close_frac(out["d_disp"][s], rec["grad/disp%d" % s], atol=2e-8, rtol=2e-3)
+        close_frac(out["d_disp"][s], rec["grad/disp%d" % s], **GRAD_TOL)
         if "out/depth%d" % s in rec:
             e = out["extras"][s]
             close(e["depth"], rec["out/depth%d" % s], 2e-6, 2e-5)
@@ -106,10 +110,10 @@ def test_chain_vs_oracle(gpu_device, B, H, W, ns, auto_mask):
                                                        num_scales=ns, auto_mask=auto_mask)
     out = run_chain(gpu_device, sample, disps, poses, noise if auto_mask else None, ns, materialize=False,
                     auto_mask=auto_mask)
-    close(out["total"], ref_losses["loss"], 1e-7, 1e-5)
+    close(out["total"], ref_losses["loss"], *LOSS_TOL)
     for s in range(ns):
-        close(out["losses"][s], ref_losses["loss/%d" % s], 1e-7, 1e-5)
-        close_frac(out["d_disp"][s], ref_grads["disp"][s], atol=2e-8, rtol=2e-3)
+        close(out["losses"][s], ref_losses["loss/%d" % s], *LOSS_TOL)
+        close_frac(out["d_disp"][s], ref_grads["disp"][s], **GRAD_TOL)
     for i in range(4):
         close_pose(out["d_pose"][i], ref_grads["pose"][i], B * H * W)
 
@@ -124,9 +128,9 @@ def test_chain_full_resolution_checksums(gpu_device):
     torch.manual_seed(7)
     noise = [torch.randn(B, 2, H, W) for _ in range(4)]
     out = run_chain(gpu_device, sample, disps, poses, noise, 4)
-    close(out["total"], rec["loss"], 1e-7, 1e-5)
+    close(out["total"], rec["loss"], *LOSS_TOL)
     for s in range(4):
-        close(out["losses"][s], rec["loss/%d" % s], 1e-7, 1e-5)
+        close(out["losses"][s], rec["loss/%d" % s], *LOSS_TOL)
         g = out["d_disp"][s].double().cpu().numpy()
         assert abs(np.abs(g).sum() - rec["grad/disp%d#abs" % s]) < 5e-3 * rec["grad/disp%d#abs" % s]
         e = out["extras"][s]

@@ -12,6 +12,14 @@ def close(a, b, atol, rtol):
     np.testing.assert_allclose(a.detach().cpu().numpy(), b, atol=atol, rtol=rtol)
 
 
+# (atol, rtol) of every comparison below, by name, so that other tests of the same operators (test_layout_ops_gpu.py) judge by them.
+# ssim: sigma = E[x^2] - mu^2 cancels ~3 digits (0.25 - 0.249): an FMA-contracted sum differs from torch's
+# by ~3e-8, i.e. ~1e-5 relative on d ~ 2e-3 -> a few 1e-5 on the SSIM value
+TOL = {"pose/M": (2e-6, 2e-5), "pose/grad": (2e-5, 1e-4), "backproject/cam": (2e-6, 2e-5), "project/grid": (1e-5, 1e-5),
+       "warp/d_depth": (5e-3, 5e-3), "warp/d_T": (5e-2, 5e-3), "ssim/out": (5e-5, 1e-5), "ssim/grad": (2e-3, 2e-3),
+       "smooth/out": (1e-8, 1e-5), "smooth/grad": (1e-7, 1e-3)}
+
+
 @pytest.fixture(scope="module")
 def ops_rec():
     return load_golden("ops_b2_48x64.npz")
@@ -24,10 +32,10 @@ def test_transformation_from_parameters(gpu_device, ops_rec, inv):
     aa = torch.from_numpy(ops_rec["pose/aa"]).to(gpu_device).requires_grad_(True)
     t = torch.from_numpy(ops_rec["pose/t"]).to(gpu_device).requires_grad_(True)
     M = L.transformation_from_parameters(aa, t, invert=inv)
-    close(M, ops_rec["pose/%s/M" % tag], 2e-6, 2e-5)
+    close(M, ops_rec["pose/%s/M" % tag], *TOL["pose/M"])
     (M * torch.from_numpy(ops_rec["pose/cot"]).to(gpu_device)).sum().backward()
-    close(aa.grad, ops_rec["pose/%s/d_aa" % tag], 2e-5, 1e-4)
-    close(t.grad, ops_rec["pose/%s/d_t" % tag], 2e-5, 1e-4)
+    close(aa.grad, ops_rec["pose/%s/d_aa" % tag], *TOL["pose/grad"])
+    close(t.grad, ops_rec["pose/%s/d_t" % tag], *TOL["pose/grad"])
     assert torch.isfinite(aa.grad).all()          # |v| = 0 row: subgradient 0, no NaN
 
 
@@ -36,7 +44,7 @@ def test_rot_and_translation_helpers(gpu_device, ops_rec):
     aa = torch.from_numpy(ops_rec["pose/aa"]).to(gpu_device)
     t = torch.from_numpy(ops_rec["pose/t"]).to(gpu_device)
     R, T = L.rot_from_axisangle(aa), L.get_translation_matrix(t)
-    close(torch.matmul(T, R), ops_rec["pose/fwd/M"], 2e-6, 2e-5)
+    close(torch.matmul(T, R), ops_rec["pose/fwd/M"], *TOL["pose/M"])
 
 
 def test_backproject_project(gpu_device, ops_rec):
@@ -48,13 +56,13 @@ def test_backproject_project(gpu_device, ops_rec):
     K, inv_K = torch.from_numpy(ops_rec["warp/K"]).to(dev), torch.from_numpy(ops_rec["warp/inv_K"]).to(dev)
     B, _, H, W = depth.shape
     cam = L.BackprojectDepth(B, H, W)(depth, inv_K)
-    close(cam, ops_rec["warp/cam"], 2e-6, 2e-5)
+    close(cam, ops_rec["warp/cam"], *TOL["backproject/cam"])
     grid = L.Project3D(B, H, W)(cam, K, T)
-    close(grid, ops_rec["warp/grid"], 1e-5, 1e-5)
+    close(grid, ops_rec["warp/grid"], *TOL["project/grid"])
     color = F.grid_sample(torch.from_numpy(ops_rec["warp/src"]).to(dev), grid, padding_mode="border", align_corners=True)
     (color * torch.from_numpy(ops_rec["warp/cot"]).to(dev)).sum().backward()
-    close(depth.grad, ops_rec["warp/d_depth"], 5e-3, 5e-3)
-    close(T.grad, ops_rec["warp/d_T"], 5e-2, 5e-3)
+    close(depth.grad, ops_rec["warp/d_depth"], *TOL["warp/d_depth"])
+    close(T.grad, ops_rec["warp/d_T"], *TOL["warp/d_T"])
 
 
 def test_ssim(gpu_device, ops_rec):
@@ -62,11 +70,9 @@ def test_ssim(gpu_device, ops_rec):
     pred = torch.from_numpy(ops_rec["ssim/pred"]).to(gpu_device).requires_grad_(True)
     tgt = torch.from_numpy(ops_rec["ssim/target"]).to(gpu_device)
     s = L.SSIM()(pred, tgt)
-    # sigma = E[x^2] - mu^2 cancels ~3 digits (0.25 - 0.249): an FMA-contracted sum differs from torch's
-    # by ~3e-8, i.e. ~1e-5 relative on d ~ 2e-3 -> a few 1e-5 on the SSIM value
-    close(s, ops_rec["ssim/out"], 5e-5, 1e-5)
+    close(s, ops_rec["ssim/out"], *TOL["ssim/out"])
     (s * torch.from_numpy(ops_rec["ssim/cot"]).to(gpu_device)).sum().backward()
-    close(pred.grad, ops_rec["ssim/d_pred"], 2e-3, 2e-3)
+    close(pred.grad, ops_rec["ssim/d_pred"], *TOL["ssim/grad"])
 
 
 def test_ssim_symmetric_gradient(gpu_device, ops_rec):
@@ -88,9 +94,9 @@ def test_smoothness(gpu_device, ops_rec):
     img = torch.from_numpy(ops_rec["smooth/img"]).to(gpu_device)
     mean_disp = torch.clamp(d.mean(2, True).mean(3, True), min=0.001)
     sm = L.get_smooth_loss(d / (mean_disp + 1e-7), img)
-    close(sm, ops_rec["smooth/out"], 1e-8, 1e-5)
+    close(sm, ops_rec["smooth/out"], *TOL["smooth/out"])
     sm.backward()
-    close(d.grad, ops_rec["smooth/d_disp"], 1e-7, 1e-3)
+    close(d.grad, ops_rec["smooth/d_disp"], *TOL["smooth/grad"])
 
 
 def test_disp_to_depth(gpu_device, ops_rec):

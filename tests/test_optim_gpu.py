@@ -5,6 +5,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+ADAM_TOL = dict(atol=1e-6, rtol=1e-5)           # FusedAdam against torch.optim.Adam after a few steps
+
+
 def test_fused_adam_matches_torch(gpu_device):
     from deep_visual_slam_amd import dp
     torch.manual_seed(0)
@@ -23,7 +26,7 @@ def test_fused_adam_matches_torch(gpu_device):
         opt.step(grad_scale=1.0, zero_grad=True)
         assert float(flat.grads.abs().max()) == 0.0
     for p1, p2 in zip(m1.parameters(), m2.parameters()):
-        assert torch.allclose(p1, p2, atol=1e-6, rtol=1e-5)
+        assert torch.allclose(p1, p2, **ADAM_TOL)
 
 
 def test_grad_scale_equals_prescaled_gradient(gpu_device):

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+TO_TENSOR_ATOL = 6e-8            # x * (1/255) vs x / 255: at most one ulp
 
 
 def test_u8_to_f32_planar_is_to_tensor(gpu_device):
@@ -17,7 +18,7 @@ def test_u8_to_f32_planar_is_to_tensor(gpu_device):
         ref = OI.to_tensor(u8)
         got = u8_to_f32_planar(torch.from_numpy(u8).to(gpu_device))
         assert got.shape == ref.shape
-        assert float((got.cpu() - ref).abs().max()) <= 6e-8          # x * (1/255) vs x / 255: at most one ulp
+        assert float((got.cpu() - ref).abs().max()) <= TO_TENSOR_ATOL
         bgr = u8_to_f32_planar(torch.from_numpy(u8).to(gpu_device), bgr=True)
         assert torch.equal(bgr.cpu(), got.cpu().flip(1))
 
