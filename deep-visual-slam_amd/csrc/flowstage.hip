@@ -16,7 +16,7 @@
 // split nor the tile sizes can change the result.  At 60x80 that is 75 workgroups of 16 waves.
 //
 // flow_to_image.  The flow is addressed through element strides (image stride = 2 * plane_stride), so the un-padded view of a
-// padded flow is coloured in place.  radmax: one hipMemsetAsync, then per workgroup a shuffle / LDS maximum and one INTEGER
+// padded flow is coloured in place.  radmax: a zero-fill launch (a kernel: see radmax_zero_kernel), then per workgroup a shuffle / LDS maximum and one INTEGER
 // atomicMax on the bit pattern of the non-negative fp32 radius (ordered like the values; a NaN sorts above +inf and wins, as in
 // np.max); a maximum is exact in any order, so the launch geometry cannot change it.  Colouring: a lane owns four consecutive
 // pixels of the dense [N][H][W][3] output = 12 bytes = three aligned dwords, stored as one dwordx3; the reads are two float4
@@ -156,6 +156,14 @@ __device__ __forceinline__ void load_pixels(const View& s, int n, unsigned q, in
     }
 #pragma unroll
     for (int k = 0; k < kPix; ++k) u[k] = clipped(u[k], s.clip_flow), v[k] = clipped(v[k], s.clip_flow);
+}
+
+// Zero fill of radmax.  A kernel, not hipMemsetAsync: inside a captured HIP graph a memset node is not reliably ordered before
+// the kernel node that accumulates into the buffer once a second graph has been captured (conv_fwd.hip: splitk_zero_kernel);
+// a replay then takes the maximum over this and an earlier frame.  Kernel -> kernel edges are ordered.
+__global__ void __launch_bounds__(kThreads) radmax_zero_kernel(unsigned* __restrict__ radmax, int N) {
+    const int n = blockIdx.x * kThreads + threadIdx.x;
+    if (n < N) radmax[n] = 0u;
 }
 
 template <bool VEC>
@@ -310,8 +318,8 @@ int dvs_flow_radmax(const float* flow, long long plane_stride, long long row_str
     DVS_REQUIRE(radmax, "dvs_flow_radmax: null pointer");
     DVS_REQUIRE(aligned(radmax, 4), "dvs_flow_radmax: misaligned pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemsetAsync(radmax, 0, sizeof(float) * (size_t)N, st);
-    if (e != hipSuccess) return dvs::fail(DVS_ERR_LAUNCH, "dvs_flow_radmax: hipMemsetAsync: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(radmax_zero_kernel, dim3(((unsigned)N + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                       reinterpret_cast<unsigned*>(radmax), N);
     const unsigned per_block = kThreads * kPix, HW = (unsigned)H * (unsigned)W;
     const dim3 grid((HW + per_block - 1) / per_block, (unsigned)N);
     unsigned* bits = reinterpret_cast<unsigned*>(radmax);

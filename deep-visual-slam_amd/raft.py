@@ -5,6 +5,8 @@ upsampling upsample_flow (csrc/convexup.hip); RAFT's own usage is in its docstri
     raft = SmallRAFT(); raft.load_state_dict(torch.load("raft-small.pth")); raft = raft.cuda()
     flows = raft(image1, image2, iters=12)              # list of 12 [B,2,H,W] flows, images in 0 .. 1
     flow = raft(image1, image2, last_only=True)[-1]     # only the final flow is upsampled (an extension)
+    feat = raft.encode_frame(image4)                    # one frame's (fmap, net, inp); image4 is dvs_frame_ingest's output
+    flows = raft.refine(feat1, feat2, iters=12)         # forward's result for the pair, each frame encoded once (raft_video.FlowStream)
 
 Submodules are fnet, cnet and update_block with the reference's parameter names, so a raft-small.pth state dict loads with
 load_state_dict(strict=True).  `inp` is made once and handed to the update block as the same tensor object in every iteration, so
@@ -142,32 +144,49 @@ class _RaftBase(nn.Module):
             raise DvsError("%s: image1 %s on %s, image2 %s on %s"
                            % (who, tuple(image1.shape), image1.device, tuple(image2.shape), image2.device))
         B, _, H, W = image1.shape
+        self._check_size(who, H, W)
+        self._check_rest(who, B, H, W, image1.device, iters, flow_init)
+
+    @staticmethod
+    def _check_size(who, H, W):
         if H % 8 or W % 8 or H < 128 or W < 128:
             raise DvsError("%s: images must be multiples of 8 and at least 128x128 (the 4-level correlation pyramid needs "
                            "16x16 features), got %dx%d" % (who, H, W))
+
+    @staticmethod
+    def _check_rest(who, B, H, W, device, iters, flow_init):
         if int(iters) < 1:
             raise DvsError("%s: iters=%r must be at least 1" % (who, iters))
         if flow_init is not None:
-            if (not torch.is_tensor(flow_init) or flow_init.device != image1.device or flow_init.dtype != torch.float32
+            if (not torch.is_tensor(flow_init) or flow_init.device != device or flow_init.dtype != torch.float32
                     or tuple(flow_init.shape) != (B, 2, H // 8, W // 8)):
-                raise DvsError("%s: flow_init must be a fp32 [%d,2,%d,%d] tensor on %s" % (who, B, H // 8, W // 8, image1.device))
+                raise DvsError("%s: flow_init must be a fp32 [%d,2,%d,%d] tensor on %s" % (who, B, H // 8, W // 8, device))
 
     def _iterate(self, image1, image2, iters, flow_init, want_mask=None):
         """raft.py:76-117 and 183-239 up to the upsampling: (the 1/8-resolution flow of every iteration, the update block's mask
         of every iteration).  want_mask(it, iters) decides whether iteration `it` runs the block's mask head; None is for a
         block without one."""
         self._check(image1, image2, iters, flow_init)
-        iters = int(iters)
         image1 = 2 * image1 - 1.0
         image2 = 2 * image2 - 1.0
         fmap1, fmap2 = self.fnet([image1, image2])
-        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
-        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
-        net, inp = torch.split(self.cnet(image1), [self.hidden_dim, self.context_dim], dim=1)
+        return self._loop(fmap1, fmap2, lambda: self._context(self.cnet(image1)), iters, flow_init, want_mask)
+
+    def _context(self, c):
+        """(net, inp) of the context encoder's output, in the memory the update block takes."""
+        net, inp = torch.split(c, [self.hidden_dim, self.context_dim], dim=1)
         net = conv._nhwc(torch.tanh(net))
         inp = conv._nhwc(torch.relu(inp))                   # made once: the update block's hoisted terms are keyed on this object
-        B, _, H, W = image1.shape
-        coords0 = coords_grid(B, H // 8, W // 8, image1.device)
+        return net, inp
+
+    def _loop(self, fmap1, fmap2, context, iters, flow_init, want_mask):
+        """The correlation block on (fmap1, fmap2), then context() -> (net, inp), then `iters` update steps."""
+        iters = int(iters)
+        block = AlternateCorrBlock if self.alternate_corr else CorrBlock
+        corr_fn = block(fmap1, fmap2, num_levels=self.corr_levels, radius=self.corr_radius)
+        net, inp = context()
+        B, _, h, w = fmap1.shape
+        coords0 = coords_grid(B, h, w, fmap1.device)
         coords1 = coords0
         if flow_init is not None:
             coords1 = coords1 + flow_init
@@ -183,6 +202,35 @@ class _RaftBase(nn.Module):
             masks.append(mask)
         self.flow_low = [f.detach() for f in flows]         # the 1/8-resolution flows of the last call (RAFT's test_mode output)
         return flows, masks
+
+    # ---- one frame at a time: a sequence encodes every frame once (raft_video.FlowStream) ----------------------------------------
+    def encode_frame(self, image4):
+        """The features of ONE frame batch: a namespace (fmap = fnet(frame); net, inp = the tanh / relu halves of cnet(frame), in
+        the memory the update block takes).  image4 is conv1's own operand, [N,4,H,W] in NHWC memory: the frame as 2 * x - 1 with a
+        zero fourth channel, which dvs_frame_ingest writes.  fnet's instance norm is per image and cnet has no norm (SmallRAFT) or
+        a BatchNorm on its running statistics in eval() (RAFT), so the features of a frame do not depend on its partner."""
+        who = type(self).__name__
+        gpu_arg("%s.encode_frame: image4" % who, image4, "[N,4,H,W] expected", ok=lambda shape: shape[1] == 4)
+        self._check_size(who + ".encode_frame", *image4.shape[2:])
+        fmap = self.fnet(image4, _image4_operand=True)
+        net, inp = self._context(self.cnet(image4, _image4_operand=True))
+        return SimpleNamespace(fmap=fmap, net=net, inp=inp)
+
+    def _refine(self, feat1, feat2, iters, flow_init, want_mask=None):
+        who = type(self).__name__ + ".refine"
+        for name, f in (("feat1", feat1), ("feat2", feat2)):
+            for field in ("fmap", "net", "inp"):
+                gpu_arg("%s: %s.%s" % (who, name, field), getattr(f, field, None), "[N,C,h,w] expected")
+        f1, f2 = feat1.fmap, feat2.fmap
+        if f1.shape != f2.shape or f1.device != f2.device:
+            raise DvsError("%s: feat1.fmap %s on %s, feat2.fmap %s on %s" % (who, tuple(f1.shape), f1.device, tuple(f2.shape), f2.device))
+        B, _, h, w = f1.shape
+        if (tuple(feat1.net.shape) != (B, self.hidden_dim, h, w) or tuple(feat1.inp.shape) != (B, self.context_dim, h, w)
+                or feat1.net.device != f1.device or feat1.inp.device != f1.device):
+            raise DvsError("%s: feat1.net %s / feat1.inp %s do not belong to feat1.fmap %s (encode_frame makes all three)"
+                           % (who, tuple(feat1.net.shape), tuple(feat1.inp.shape), tuple(f1.shape)))
+        self._check_rest(who, B, 8 * h, 8 * w, f1.device, iters, flow_init)
+        return self._loop(f1, f2, lambda: (feat1.net, feat1.inp), iters, flow_init, want_mask)
 
     def _upsampled(self, flows, masks, only_last):
         """The list of full-resolution flows, of the last iteration alone or of all of them by ONE launch (N = iters * B): upflow8
@@ -233,15 +281,22 @@ class RAFT(_RaftBase):
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
 
-    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
+    def _outputs(self, iterate, upsample, test_mode, last_only):
         only_last = bool(test_mode or last_only)
-        flows, masks = self._iterate(image1, image2, iters, flow_init,
-                                     lambda it, n: bool(upsample) and (not only_last or it == n - 1))
+        flows, masks = iterate(lambda it, n: bool(upsample) and (not only_last or it == n - 1))
         # upsample=False is the block's: no mask, bilinear upflow8 as raft.py:234-235
         up = self._upsampled(flows, masks if upsample else None, only_last)
         if test_mode:
             return flows[-1], up[-1]
         return up
+
+    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
+        return self._outputs(lambda want_mask: self._iterate(image1, image2, iters, flow_init, want_mask), upsample, test_mode, last_only)
+
+    def refine(self, feat1, feat2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
+        """What forward returns for the pair whose frames encode_frame made feat1 and feat2 of: the correlation block on their
+        fmaps, the loop on feat1.net / feat1.inp, the upsampling."""
+        return self._outputs(lambda want_mask: self._refine(feat1, feat2, iters, flow_init, want_mask), upsample, test_mode, last_only)
 
 
 class SmallRAFT(_RaftBase):
@@ -260,4 +315,9 @@ class SmallRAFT(_RaftBase):
 
     def forward(self, image1, image2, iters=12, flow_init=None, last_only=False):
         flows, _ = self._iterate(image1, image2, iters, flow_init)
+        return self._upsampled(flows, None, last_only)
+
+    def refine(self, feat1, feat2, iters=12, flow_init=None, last_only=False):
+        """What forward returns for the pair whose frames encode_frame made feat1 and feat2 of."""
+        flows, _ = self._refine(feat1, feat2, iters, flow_init)
         return self._upsampled(flows, None, last_only)

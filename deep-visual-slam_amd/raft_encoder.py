@@ -155,8 +155,16 @@ class _Encoder(DerivedOperands, nn.Module):
             return instance_norm_act(conv.conv2d(x, wt, b, stride=stride, padding=padding), relu=relu)
         return conv.conv2d(x, wt, b, stride=stride, padding=padding, act="relu" if relu else None)
 
-    def forward(self, x):
+    def forward(self, x, _image4_operand=False):
+        """_image4_operand (private, raft.encode_frame's): x already is conv1's operand, the normalised image [N,4,H,W] in NHWC
+        memory with a zero fourth channel, which dvs_frame_ingest writes: nothing stands between the ingest and conv1."""
         who = type(self).__name__
+        if _image4_operand:
+            gpu_arg(who + ": input", x, "[N,4,H,W] expected", ok=lambda shape: shape[1] == 4)
+            if not x.is_contiguous(memory_format=CL) or x.data_ptr() % 16:
+                raise DvsError("%s: the 4-channel operand must be dense NHWC memory on a 16-byte boundary, got strides %s" % (who, x.stride()))
+            self._check_size(x)
+            return self._from_image4(x, self._derive())
         is_list = isinstance(x, (tuple, list))
         if is_list:
             if len(x) != 2:
@@ -170,20 +178,28 @@ class _Encoder(DerivedOperands, nn.Module):
         gpu_arg(who + ": input", x, "[N,C,H,W] expected")
         if x.shape[1] != 3:
             raise DvsError("%s: 3 input channels expected, got %s" % (who, tuple(x.shape)))
+        self._check_size(x)
+        w = self._derive()
+        x = self._from_image4(_image4(x), w)
+        if is_list:
+            return torch.split(x, [batch_dim, batch_dim], dim=0)
+        return x
+
+    def _check_size(self, x):
+        who = type(self).__name__
         if x.shape[2] < 16 or x.shape[3] < 16:
             raise DvsError("%s: images of at least 16x16 expected (the instance norm needs 2 features), got %s" % (who, tuple(x.shape)))
         for p in self.parameters():
             if p.device != x.device or p.dtype != torch.float32:
                 raise DvsError("%s: parameters on %s / %s, input on %s / fp32; move the module with .to()"
                                % (who, p.device, p.dtype, x.device))
-        w = self._derive()
-        x = self._unit(_image4(x), w, self.conv1, getattr(self, "norm1", None), 2, 3)
+
+    def _from_image4(self, x4, w):
+        """conv1 onwards on the operand conv1 reads: the normalised image [N,4,H,W] in NHWC memory, fourth channel zero."""
+        x = self._unit(x4, w, self.conv1, getattr(self, "norm1", None), 2, 3)
         for b in self._blocks():
             x = self._block(b, w, x)
-        x = conv.conv2d(x, *w[self.conv2])
-        if is_list:
-            return torch.split(x, [batch_dim, batch_dim], dim=0)
-        return x
+        return conv.conv2d(x, *w[self.conv2])
 
 
 class _Bottleneck(nn.Module):

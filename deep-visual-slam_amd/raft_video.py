@@ -4,14 +4,22 @@
     flow_to_image(flow, ...)       utils/flow_viz.py:109-132: the colour-wheel picture of a flow, uint8
     InputPadder(dims, mode)        utils/utils.py:7-24: replicate padding to multiples of 8, and the view that undoes it
     FlowPredictor(model, ...)      pad -> model(test_mode) -> warm start -> un-pad -> colour, one call per frame pair
+    frame_ingest(frame, pad)       csrc/ingest.hip: a uint8 frame as the encoders' first operand (/255, replicate pad, 2x - 1, NHWC)
+    FlowStream(model, ...)         one push per uint8 frame: ingest -> encode once -> refine(previous, current) -> warm start -> colour;
+                                   graph=True replays it as one HIP graph, host=True adds pinned host copies
 
     pred = FlowPredictor(raft.RAFT({"small": False}).cuda().eval(), iters=12)
     for frame1, frame2 in pairs:                       # [B,3,H,W] fp32 in 0 .. 1 on the GPU, any H, W the padded model accepts
         r = pred(frame1, frame2)                       # r.flow_up [B,2,H,W] (a view), r.flow_low, r.image [B,H,W,3] uint8
     pred.reset()                                       # a new sequence: drop the kept flow
 
+    stream = FlowStream(model, iters=12)               # graph=True by default: one HIP graph replay per frame
+    for frame in frames:                               # uint8 [H,W,3] or [N,H,W,3], on the GPU or on the host
+        r = stream.push(frame)                         # None for the first frame, then r.flow_up, r.flow_low, r.image (until the next push)
+
 forward_interpolate and flow_to_image are csrc/flowstage.hip (include/dvslam.h states their arithmetic); nothing here copies to
-the host or synchronises.  Padding is F.pad and a slice: not hot, it stays ATen.  GPU and fp32 only.
+the host or synchronises (FlowStream's host=True copies are asynchronous; reading one waits for its event).  FlowPredictor's
+padding is F.pad and a slice: not hot, it stays ATen.  GPU only; fp32 flows, uint8 frames and pictures.
 """
 from types import SimpleNamespace
 
@@ -156,3 +164,273 @@ class FlowPredictor:
         return SimpleNamespace(flow_low=flow_low, flow_up=flow_up, image=image)
 
     __call__ = pred
+
+
+# ---- one frame at a time ---------------------------------------------------------------------------------------------------------
+def _frames_u8(who, frame):
+    """A uint8 [H,W,3] or [N,H,W,3] tensor (host or device) as its [N,H,W,3] view."""
+    if not torch.is_tensor(frame):
+        raise DvsError("%s: a uint8 tensor [H,W,3] or [N,H,W,3] expected, got %s" % (who, type(frame).__name__))
+    if frame.dtype != torch.uint8:
+        raise DvsError("%s: uint8 only, got %s (the frame as the decoder delivers it; float pairs are FlowPredictor's)" % (who, frame.dtype))
+    if frame.dim() not in (3, 4) or frame.shape[-1] != 3 or min(frame.shape) < 1:
+        raise DvsError("%s: [H,W,3] or [N,H,W,3] expected, got %s" % (who, tuple(frame.shape)))
+    return frame if frame.dim() == 4 else frame[None]
+
+
+def _packed(f):
+    """(tensor, image stride, row stride) in bytes with which dvs_frame_ingest reads `f` [N,H,W,3]: `f` itself where its pixels are
+    three adjacent bytes, its rows do not overlap and its images neither (a dense frame, a batch slice, a crop of a larger frame,
+    a frame at any storage offset), else ONE dense copy (a planar [3,H,W] frame seen through permute, a transposed or an expanded
+    one): a layout the kernel does not address is never read as if it were dense."""
+    N, H, W, _ = f.shape
+    s0, s1, s2, s3 = f.stride()
+    row = s1 if H > 1 else 3 * W
+    image = s0 if N > 1 else (H - 1) * row + 3 * W
+    if s3 == 1 and (s2 == 3 or W == 1) and row >= 3 * W and image >= (H - 1) * row + 3 * W:
+        return f, image, row
+    return f.contiguous(), 3 * H * W, 3 * W
+
+
+def frame_ingest(frame, pad=(0, 0, 0, 0), bgr=False):
+    """dvs_frame_ingest (include/dvslam.h states the arithmetic): uint8 frames [H,W,3] or [N,H,W,3] on the GPU, RGB (BGR with
+    bgr=True), to the RAFT encoders' first operand: 2 * (x / 255) - 1, replicate-padded by pad = (left, right, top, bottom) as
+    InputPadder._pad orders them (0 .. 7 each), with a zero fourth channel, fp32 [N,4,Hp,Wp] in NHWC memory.  Bit for bit what
+    the reference's .float() / 255.0, InputPadder.pad and 2 * image - 1.0 give on the CPU.  Frames whose pixels are three
+    adjacent bytes are read in place through their strides; any other layout is copied once."""
+    who = "frame_ingest"
+    f = _frames_u8(who, frame)
+    if not f.is_cuda:
+        raise DvsError("%s: GPU tensors only (got %s); this package has no CPU path" % (who, f.device))
+    pad = tuple(int(p) for p in pad)
+    if len(pad) != 4 or min(pad) < 0 or max(pad) > 7:
+        raise DvsError("%s: pad=%r must be (left, right, top, bottom), each in 0 .. 7" % (who, pad))
+    f, image_stride, row_stride = _packed(f)
+    N, H, W, _ = f.shape
+    left, right, top, bottom = pad
+    out = torch.empty((N, top + H + bottom, left + W + right, 4), device=f.device, dtype=torch.float32)
+    check(_lib.lib().dvs_frame_ingest(f.data_ptr(), image_stride, row_stride, out.data_ptr(), N, H, W, left, right, top, bottom,
+                                      int(bool(bgr)), _lib.stream()), "dvs_frame_ingest")
+    return out.permute(0, 3, 1, 2)
+
+
+class FlowFrame:
+    """What FlowStream.push returns for a pair: flow_low [N,2,Hp/8,Wp/8] at the padded size, flow_up [N,2,H,W] (a view of the padded
+    flow), image uint8 [N,H,W,3] or None, all on the device.  With host=True, image_host and flow_low_host are numpy views of
+    pinned host memory that is filled asynchronously: reading one waits for this frame's copy event first (`wait()`), and the
+    views stay valid until the push after next (two buffers)."""
+
+    def __init__(self, flow_low, flow_up, image, slot=None):
+        self.flow_low, self.flow_up, self.image, self._slot = flow_low, flow_up, image, slot
+
+    def wait(self):
+        if self._slot is None:
+            raise DvsError("FlowStream: host copies are made with host=True only")
+        self._slot["event"].synchronize()
+        return self
+
+    @property
+    def flow_low_host(self):
+        return self.wait()._slot["flow_low"].numpy()
+
+    @property
+    def image_host(self):
+        image = self.wait()._slot["image"]
+        return image.numpy() if image is not None else None
+
+
+class FlowStream:
+    """RAFT on a stream of uint8 frames, one push per frame: every frame is ingested by ONE launch (dvs_frame_ingest: /255, the
+    replicate padding, 2 * x - 1, conv1's 4-channel NHWC operand) and encoded ONCE (fnet and cnet over N images), its features
+    are kept for the next push, and each pair is model.refine(previous, current) with forward_interpolate(flow_low) kept as the
+    next flow_init, exactly as in FlowPredictor.
+
+        stream = FlowStream(raft.RAFT({"small": False}).cuda().eval(), iters=12)
+        for frame in frames:                    # uint8 [H,W,3] or [N,H,W,3], RGB (bgr=True: BGR); on the GPU, or on the host
+            r = stream.push(frame)              # None for the first frame of a sequence, then a FlowFrame for (previous, this)
+        stream.reset()                          # a new sequence
+
+    A host frame is copied with one non_blocking H2D copy (pin it to make that asynchronous).  The copy then reads the caller's
+    buffer after push has returned: do not write the next frame into it before `stream.frame_copied.synchronize()` (an event
+    recorded behind the copy; None after a push of a device frame), or hand push a buffer of its own per frame in flight.  A device frame whose pixels are
+    three adjacent bytes (dense, a batch slice, a crop of a larger frame) is read in place; any other layout is copied once.
+    Frames are taken as they are: a caller who wants the demo's Image.resize((640, 480), BILINEAR) runs input_pipeline's PIL-exact
+    uint8 resize first and pushes its output.
+
+    graph=True (the default: measured faster than the eager stream for both models; graph=False issues the
+    same launches eagerly and returns fresh tensors): everything after the copy of the frame into a static uint8 buffer -- ingest, both encoders, the correlation
+    block, all `iters` update steps, the upsampling, forward_interpolate into the persistent flow_init buffer, the colouring and
+    the hand-over of this frame's features to the "previous" slot -- is one HIP graph, captured on one stream at the first push
+    of a shape.  The returned tensors are then the graph's static outputs: consume (or clone) them before the next push.  A zeroed
+    flow_init is the cold start, so reset() zeroes the buffer and marks the slot empty without a new capture; the graph is
+    captured again by itself when the weights or the BatchNorm buffers changed (stale()).
+    host=True: the picture and flow_low are also copied asynchronously into two alternating pinned host buffers (FlowFrame)."""
+
+    def __init__(self, model, iters=12, warm_start=True, pad_mode="sintel", image=True, convert_to_bgr=False, bgr=False,
+                 graph=True, host=False, warmup=2):
+        if not isinstance(model, (RAFT, SmallRAFT)):
+            raise DvsError("FlowStream: model must be a raft.RAFT or a raft.SmallRAFT, got %s" % type(model).__name__)
+        if int(iters) < 1:
+            raise DvsError("FlowStream: iters=%r must be at least 1" % (iters,))
+        self.model, self.iters, self.warm_start, self.pad_mode = model, int(iters), bool(warm_start), pad_mode
+        self.image, self.convert_to_bgr, self.bgr = bool(image), bool(convert_to_bgr), bool(bgr)
+        self.use_graph, self.host, self.warmup = bool(graph), bool(host), int(warmup)
+        self.flow_init = None               # eager: the kept flow or None; graph: the persistent buffer
+        self._prev, self._shape = None, None  # the previous frame's features (graph: the slot, with _have_prev)
+        self._have_prev = False
+        self.graph, self._graph_shape = None, None
+        self._slots, self._n = None, 0
+        self.frame_copied = None            # the event behind the last host frame's H2D copy
+
+    def reset(self):
+        """A new sequence: the next push encodes its frame and returns None."""
+        self._shape, self._have_prev = None, False
+        if self.graph is None:
+            self.flow_init, self._prev = None, None
+        elif self.warm_start:
+            self.flow_init.zero_()
+
+    # ---- one step, eager or under capture --------------------------------------------------------------------------------------
+    def _refine(self, prev, feat, flow_init):
+        """(flow_low, flow_up at the padded size): RAFT has a test mode; SmallRAFT's counterpart is last_only and its flow_low."""
+        if isinstance(self.model, RAFT):
+            return self.model.refine(prev, feat, iters=self.iters, flow_init=flow_init, test_mode=True)
+        up = self.model.refine(prev, feat, iters=self.iters, flow_init=flow_init, last_only=True)[-1]
+        return self.model.flow_low[-1], up
+
+    def _encode(self, frames, padder):
+        return self.model.encode_frame(frame_ingest(frames, padder._pad, self.bgr))
+
+    def _pair(self, prev, feat, flow_init, padder):
+        flow_low, flow_pad = self._refine(prev, feat, flow_init)
+        kept = forward_interpolate(flow_low) if self.warm_start else None
+        flow_up = padder.unpad(flow_pad)
+        image = flow_to_image(flow_up, convert_to_bgr=self.convert_to_bgr) if self.image else None
+        return flow_low, flow_up, image, kept
+
+    def _graph_step(self, padder):
+        """What the graph holds: s_frame -> outputs, flow_init and the previous slot advanced in place."""
+        feat = self._encode(self.s_frame, padder)
+        flow_low, flow_up, image, kept = self._pair(self._prev, feat, self.flow_init, padder)
+        if kept is not None:
+            self.flow_init.copy_(kept)
+        for name in ("fmap", "net", "inp"):                 # copy_ bumps inp's version: the update block's hoisted terms are re-made
+            getattr(self._prev, name).copy_(getattr(feat, name))
+        return flow_low, flow_up, image
+
+    # ---- capture -----------------------------------------------------------------------------------------------------------------
+    def _derived(self):
+        return [m._weights for m in (self.model.fnet, self.model.cnet, self.model.update_block)]
+
+    def _capture(self, frames, padder):
+        """Warm-up on a side stream, then the capture.  Both advance nothing: the kept flow and the previous slot are put back."""
+        from . import inference
+        first = self._graph_shape != self._shape_of(frames)
+        if first:
+            self.graph = None
+            self.s_frame = torch.empty(tuple(frames.shape), device=frames.device, dtype=torch.uint8)
+            self.s_frame.copy_(frames)
+            with torch.no_grad():
+                feat = self._encode(self.s_frame, padder)   # a padded size the model refuses: the model's own error
+            self._prev = SimpleNamespace(fmap=feat.fmap.clone(), net=feat.net.clone(), inp=feat.inp.clone())
+            N, _, h, w = feat.fmap.shape
+            self.flow_init = torch.zeros((N, 2, h, w), device=frames.device) if self.warm_start else None
+        state = [t.clone() for t in self._state()]
+        side = torch.cuda.Stream(device=frames.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(self.warmup):
+                self._graph_step(padder)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self.static_out = self._graph_step(padder)
+        self._gen, self._held = inference._fold_snapshot()
+        self._watch = inference._WeightsWatch(self.model)
+        self._held_derived = self._derived()                # the graph points into these operands: kept alive, compared in stale()
+        self._graph_shape = self._shape_of(frames)
+        for t, saved in zip(self._state(), state):
+            t.copy_(saved)
+
+    def _state(self):
+        return [self._prev.fmap, self._prev.net, self._prev.inp] + ([self.flow_init] if self.warm_start else [])
+
+    def stale(self):
+        """True when the weights or BatchNorm buffers changed since the capture, or the operands derived from them were re-made."""
+        from . import nn_ops
+        return self.graph is not None and (self._gen != nn_ops.generation() or self._watch.changed()
+                                           or any(a is not b for a, b in zip(self._derived(), self._held_derived)))
+
+    @staticmethod
+    def _shape_of(frames):
+        return (tuple(frames.shape), frames.device)
+
+    # ---- push --------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def push(self, frame):
+        if self.model.training:
+            raise DvsError("FlowStream: the model is in train() mode; call model.eval() (inference runs BatchNorm on its running "
+                           "statistics and keeps no graph)")
+        frames = _frames_u8("FlowStream: frame", frame)
+        device = next(self.model.parameters()).device
+        if device.type != "cuda":
+            raise DvsError("FlowStream: the model is on %s; GPU only, this package has no CPU path" % (device,))
+        self.frame_copied = None
+        if not frames.is_cuda:
+            frames = frames.to(device, non_blocking=True)   # one H2D copy (asynchronous from pinned memory)
+            self.frame_copied = torch.cuda.Event()
+            self.frame_copied.record()
+        shape = self._shape_of(frames)
+        if self._shape is not None and shape != self._shape:
+            raise DvsError("FlowStream: input changed from %s on %s to %s on %s inside a sequence; call reset() first"
+                           % (self._shape + shape))
+        padder = InputPadder(frames.shape[1:3], self.pad_mode)
+        if self.use_graph:
+            out = self._push_graph(frames, padder)
+        else:
+            out = self._push_eager(frames, padder)
+        self._shape = shape
+        if out is None:
+            return None
+        slot = None
+        if self.host:
+            slot = self._host_slot(out)
+        return FlowFrame(out[0], out[1], out[2], slot)
+
+    def _push_eager(self, frames, padder):
+        feat = self._encode(frames, padder)                 # a padded size the model refuses: the model's own error
+        prev, self._prev = self._prev, feat
+        if prev is None:
+            return None
+        flow_low, flow_up, image, kept = self._pair(prev, feat, self.flow_init, padder)
+        self.flow_init = kept
+        return flow_low, flow_up, image
+
+    def _push_graph(self, frames, padder):
+        if self.graph is None or self._graph_shape != self._shape_of(frames):
+            self._have_prev = False
+            self._capture(frames, padder)
+        elif self.stale():
+            self._capture(frames, padder)
+        self.s_frame.copy_(frames, non_blocking=True)
+        self.graph.replay()
+        if self._have_prev:
+            return self.static_out
+        self._have_prev = True                              # the first frame of a sequence: only its features count
+        if self.warm_start:
+            self.flow_init.zero_()
+        return None
+
+    def _host_slot(self, out):
+        if self._slots is None or self._slots[0]["flow_low"].shape != out[0].shape or (
+                out[2] is not None and self._slots[0]["image"].shape != out[2].shape):
+            pin = lambda t: torch.zeros(tuple(t.shape), dtype=t.dtype, pin_memory=True) if t is not None else None
+            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), event=torch.cuda.Event()) for _ in range(2)]
+        slot = self._slots[self._n & 1]
+        self._n += 1
+        slot["flow_low"].copy_(out[0], non_blocking=True)
+        if out[2] is not None:
+            slot["image"].copy_(out[2], non_blocking=True)
+        slot["event"].record()
+        return slot

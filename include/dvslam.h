@@ -875,19 +875,43 @@ int dvs_forward_interp(const float* flow, float* out, int N, int h, int w, void*
  *   rounded on neither side, so a byte whose value sits on a floor() boundary may differ by one from NumPy's (tests/test_flowstage_gpu.py
  *   states the rule).  The 55 x 3 wheel is computed from the six segment lengths 15, 6, 4, 11, 13, 6; k0 is clamped to 0 .. 54 before
  *   it indexes the table and the byte to 0 .. 255, so no input value (NaN, infinity) can read or write outside.
- *   dvs_flow_radmax: one hipMemsetAsync and one launch; the only atomic is an INTEGER atomicMax on the bit pattern of a
+ *   dvs_flow_radmax: a zero-fill launch (a kernel, so that a captured graph orders it) and one launch; the only atomic is an INTEGER atomicMax on the bit pattern of a
  *   non-negative fp32, and a maximum is exact in any order: the result does not depend on the launch geometry.
  *   dvs_flow_to_image: reads radmax from device memory (no host synchronisation between the two calls); 8 bytes read and 3 written
  *   per pixel; a lane stores four pixels as three dwords, and reads them as two float4 where W, both strides and the pointer are
  *   multiples of 4 elements / 16 bytes.
  *   1 <= N <= 65535, H, W >= 1, N * H * W < 2^31, row_stride >= W, plane_stride >= (H - 1) * row_stride + W, clip_flow not NaN,
- *   bgr 0 or 1; flow and radmax 4-byte, out 16-byte aligned.  DVS_ERR_INVALID, before any launch or memset, otherwise.
+ *   bgr 0 or 1; flow and radmax 4-byte, out 16-byte aligned.  DVS_ERR_INVALID, before any launch, otherwise.
  *   dvs_set_precision does not affect these entries.
  * ------------------------------------------------------------------------------------------- */
 int dvs_flow_radmax(const float* flow, long long plane_stride, long long row_stride, int N, int H, int W, float clip_flow,
                     float* radmax, void* stream);                                           /* utils/flow_viz.py:123-128 */
 int dvs_flow_to_image(const float* flow, long long plane_stride, long long row_stride, const float* radmax, unsigned char* out, int N,
                       int H, int W, float clip_flow, int bgr, void* stream);              /* utils/flow_viz.py:70-106, 129-132 */
+
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Frame ingest: a decoder's uint8 frame as the RAFT encoders' first operand
+ *     replaces load_image's .float() and /= 255.0 (model/raft/raft.py:22-23), InputPadder.pad (model/raft/core/utils/utils.py:7-21),
+ *     2 * image - 1.0 (model/raft/core/raft.py:70-71, 188-190) and the NHWC / zero-channel form conv1 reads, in one launch
+ *
+ *   src: uint8, N frames of H x W pixels of 3 bytes (RGB; BGR with bgr = 1), pixel (n, y, x) at src + n * image_stride +
+ *   y * row_stride + 3 * x (byte strides), so a crop of a larger frame and a batch slice are read in place.
+ *   dst: fp32 [N][Hp][Wp][4] dense, Hp = top + H + bottom, Wp = left + W + right.  fp32, every operation rounded on its own (no
+ *   contraction), the division correctly rounded (the reference divides on the host):
+ *       q               = float(src[n, clamp(y - top, 0, H - 1), clamp(x - left, 0, W - 1), bgr ? 2 - c : c]) / 255.0f
+ *       dst[n, y, x, c] = 2.0f * q - 1.0f          c < 3; 2 * q is exact
+ *       dst[n, y, x, 3] = 0
+ *   which is bit for bit what the reference's chain gives on the CPU (ATen's device-side tensor / scalar may multiply by a
+ *   reciprocal and is not the yardstick).  The replicate padding is the clamp; no branch on the border.
+ *   A lane owns four consecutive output pixels of a row and stores each as one 16-byte vector; it reads their 12 source bytes as
+ *   three dwords where src, both strides, W and left are multiples of 4, single bytes otherwise.  No LDS, no atomics, no
+ *   workspace; a frame's result does not depend on the other frames of the batch.
+ *   1 <= N <= 65535, H, W >= 1, every pad in 0 .. 7, row_stride >= 3 * W, image_stride >= (H - 1) * row_stride + 3 * W, bgr 0 or 1,
+ *   Hp * ceil(Wp / 4) < 2^31; dst 16-byte aligned, src at any byte.  DVS_ERR_INVALID, before any launch, otherwise.
+ *   dvs_set_precision does not affect this entry.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_frame_ingest(const unsigned char* src, long long image_stride, long long row_stride, float* dst, int N, int H, int W,
+                     int left, int right, int top, int bottom, int bgr, void* stream);
 
 #ifdef __cplusplus
 }
