@@ -7,6 +7,7 @@ upsampling upsample_flow (csrc/convexup.hip); RAFT's own usage is in its docstri
     flow = raft(image1, image2, last_only=True)[-1]     # only the final flow is upsampled (an extension)
     feat = raft.encode_frame(image4)                    # one frame's (fmap, net, inp); image4 is dvs_frame_ingest's output
     flows = raft.refine(feat1, feat2, iters=12)         # forward's result for the pair, each frame encoded once (raft_video.FlowStream)
+    flows = raft.refine_pair(feat1, feat2, iters=12)    # both directions as one loop at batch 2N: rows [0:N] forward, [N:2N] backward
 
 Submodules are fnet, cnet and update_block with the reference's parameter names, so a raft-small.pth state dict loads with
 load_state_dict(strict=True).  `inp` is made once and handed to the update block as the same tensor object in every iteration, so
@@ -216,8 +217,9 @@ class _RaftBase(nn.Module):
         net, inp = self._context(self.cnet(image4, _image4_operand=True))
         return SimpleNamespace(fmap=fmap, net=net, inp=inp)
 
-    def _refine(self, feat1, feat2, iters, flow_init, want_mask=None):
-        who = type(self).__name__ + ".refine"
+    def _check_feats(self, who, feat1, feat2, context_of):
+        """The checks of refine / refine_pair: both frames' three tensors on the GPU, equal fmap shapes, and net / inp of every
+        frame in `context_of` belonging to its fmap.  Returns the fmap shape."""
         for name, f in (("feat1", feat1), ("feat2", feat2)):
             for field in ("fmap", "net", "inp"):
                 gpu_arg("%s: %s.%s" % (who, name, field), getattr(f, field, None), "[N,C,h,w] expected")
@@ -225,12 +227,30 @@ class _RaftBase(nn.Module):
         if f1.shape != f2.shape or f1.device != f2.device:
             raise DvsError("%s: feat1.fmap %s on %s, feat2.fmap %s on %s" % (who, tuple(f1.shape), f1.device, tuple(f2.shape), f2.device))
         B, _, h, w = f1.shape
-        if (tuple(feat1.net.shape) != (B, self.hidden_dim, h, w) or tuple(feat1.inp.shape) != (B, self.context_dim, h, w)
-                or feat1.net.device != f1.device or feat1.inp.device != f1.device):
-            raise DvsError("%s: feat1.net %s / feat1.inp %s do not belong to feat1.fmap %s (encode_frame makes all three)"
-                           % (who, tuple(feat1.net.shape), tuple(feat1.inp.shape), tuple(f1.shape)))
+        for name, f in context_of:
+            if (tuple(f.net.shape) != (B, self.hidden_dim, h, w) or tuple(f.inp.shape) != (B, self.context_dim, h, w)
+                    or f.net.device != f1.device or f.inp.device != f1.device):
+                raise DvsError("%s: %s.net %s / %s.inp %s do not belong to %s.fmap %s (encode_frame makes all three)"
+                               % (who, name, tuple(f.net.shape), name, tuple(f.inp.shape), name, tuple(f1.shape)))
+        return B, h, w
+
+    def _refine(self, feat1, feat2, iters, flow_init, want_mask=None):
+        who = type(self).__name__ + ".refine"
+        B, h, w = self._check_feats(who, feat1, feat2, (("feat1", feat1),))
+        f1, f2 = feat1.fmap, feat2.fmap
         self._check_rest(who, B, 8 * h, 8 * w, f1.device, iters, flow_init)
         return self._loop(f1, f2, lambda: (feat1.net, feat1.inp), iters, flow_init, want_mask)
+
+    def _refine_pair(self, feat1, feat2, iters, flow_init, want_mask=None):
+        """Both directions as ONE loop at batch 2N: rows 0 .. N-1 are (feat1 -> feat2), rows N .. 2N-1 are (feat2 -> feat1).  The
+        concatenated `inp` is one tensor object for the whole call, so the update block hoists its context terms once; a new call
+        makes a new object, which the block's cache (keyed on the object and its _version) sees as new, also under graph capture."""
+        who = type(self).__name__ + ".refine_pair"
+        B, h, w = self._check_feats(who, feat1, feat2, (("feat1", feat1), ("feat2", feat2)))
+        f1, f2 = feat1.fmap, feat2.fmap
+        self._check_rest(who, 2 * B, 8 * h, 8 * w, f1.device, iters, flow_init)
+        net, inp = torch.cat((feat1.net, feat2.net), 0), torch.cat((feat1.inp, feat2.inp), 0)
+        return self._loop(torch.cat((f1, f2), 0), torch.cat((f2, f1), 0), lambda: (net, inp), iters, flow_init, want_mask)
 
     def _upsampled(self, flows, masks, only_last):
         """The list of full-resolution flows, of the last iteration alone or of all of them by ONE launch (N = iters * B): upflow8
@@ -298,6 +318,12 @@ class RAFT(_RaftBase):
         fmaps, the loop on feat1.net / feat1.inp, the upsampling."""
         return self._outputs(lambda want_mask: self._refine(feat1, feat2, iters, flow_init, want_mask), upsample, test_mode, last_only)
 
+    def refine_pair(self, feat1, feat2, iters=12, flow_init=None, upsample=True, test_mode=False, last_only=False):
+        """Both directions of the pair by ONE loop at batch 2N: what refine returns at batch 2N, rows 0 .. N-1 = refine(feat1,
+        feat2), rows N .. 2N-1 = refine(feat2, feat1); flow_init is [2N,2,h,w] in that order or None.  Equal to the two refine
+        calls mathematically, not bit for bit: a convolution's route may differ with the batch."""
+        return self._outputs(lambda want_mask: self._refine_pair(feat1, feat2, iters, flow_init, want_mask), upsample, test_mode, last_only)
+
 
 class SmallRAFT(_RaftBase):
     def __init__(self, args=None):
@@ -320,4 +346,11 @@ class SmallRAFT(_RaftBase):
     def refine(self, feat1, feat2, iters=12, flow_init=None, last_only=False):
         """What forward returns for the pair whose frames encode_frame made feat1 and feat2 of."""
         flows, _ = self._refine(feat1, feat2, iters, flow_init)
+        return self._upsampled(flows, None, last_only)
+
+    def refine_pair(self, feat1, feat2, iters=12, flow_init=None, last_only=False):
+        """Both directions of the pair by ONE loop at batch 2N: what refine returns at batch 2N, rows 0 .. N-1 = refine(feat1,
+        feat2), rows N .. 2N-1 = refine(feat2, feat1); flow_init is [2N,2,h,w] in that order or None.  Equal to the two refine
+        calls mathematically, not bit for bit: a convolution's route may differ with the batch."""
+        flows, _ = self._refine_pair(feat1, feat2, iters, flow_init)
         return self._upsampled(flows, None, last_only)

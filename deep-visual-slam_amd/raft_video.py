@@ -6,7 +6,9 @@
     FlowPredictor(model, ...)      pad -> model(test_mode) -> warm start -> un-pad -> colour, one call per frame pair
     frame_ingest(frame, pad)       csrc/ingest.hip: a uint8 frame as the encoders' first operand (/255, replicate pad, 2x - 1, NHWC)
     FlowStream(model, ...)         one push per uint8 frame: ingest -> encode once -> refine(previous, current) -> warm start -> colour;
-                                   graph=True replays it as one HIP graph, host=True adds pinned host copies
+                                   graph=True replays it as one HIP graph, host=True adds pinned host copies, bidirectional=True
+                                   runs both directions as one loop at batch 2N and adds the two consistency masks
+    flow_consistency(fw, bw, ...)  csrc/flowcons.hip: the forward-backward check of UnFlow, both validity masks by one launch
 
     pred = FlowPredictor(raft.RAFT({"small": False}).cuda().eval(), iters=12)
     for frame1, frame2 in pairs:                       # [B,3,H,W] fp32 in 0 .. 1 on the GPU, any H, W the padded model accepts
@@ -88,6 +90,52 @@ def flow_to_image(flow, clip_flow=None, convert_to_bgr=False):
     check(lib.dvs_flow_to_image(f.data_ptr(), plane, row, radmax.data_ptr(), out.data_ptr(), N, H, W, clip, int(bool(convert_to_bgr)), st),
           "dvs_flow_to_image")
     return out if batched else out[0]
+
+
+def _rows(f):
+    """(tensor, image stride, plane stride, row stride) in elements with which dvs_flow_consistency reads `f` [N,2,H,W]: `f` itself
+    where its rows are dense and rows, planes and images do not overlap (a contiguous flow, a batch or channel slice, the
+    un-padded view of a padded flow, a flow at a storage offset), else ONE dense copy."""
+    N, _, H, W = f.shape
+    s0, s1, s2, s3 = f.stride()
+    row = s2 if H > 1 else W
+    extent = (H - 1) * row + W
+    image = s0 if N > 1 else s1 + extent
+    if (s3 == 1 or W == 1) and row >= W and s1 >= extent and image >= s1 + extent:
+        return f, image, s1, row
+    return f.contiguous(), 2 * H * W, H * W, W
+
+
+def flow_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5, excess=False):
+    """The forward-backward check of UnFlow (Meister et al. 2018, eq. 2) on the device, both directions in ONE launch
+    (dvs_flow_consistency; include/dvslam.h states the arithmetic).  flow_fw [2,H,W] or [N,2,H,W] fp32 on image 1's grid (image 1 ->
+    image 2), flow_bw the same on image 2's grid (image 2 -> image 1).  Returns (valid_fw, valid_bw), uint8 [H,W] or [N,H,W]: 1 where
+
+        |w + w'(x + w)|^2 <= alpha * (|w|^2 + |w'(x + w)|^2) + beta        w the pixel's own flow, w' the other flow, sampled bilinearly
+
+    and x + w lies inside the image (closed border: a zero flow is valid everywhere), 0 where the pixel is occluded, leaves the
+    image or holds a NaN.  excess=True: (valid_fw, valid_bw, excess_fw, excess_bw), the fp32 fields `left side - right side`
+    (+inf where x + w is outside or the difference is NaN), so that a caller can apply a threshold of its own.  Views whose rows
+    are dense (InputPadder.unpad's, a batch slice) are read in place through their strides; any other layout is copied once."""
+    who = "flow_consistency"
+    fw, batched = _flow_arg(who + ": flow_fw", flow_fw, "[2,H,W] or [N,2,H,W]")
+    bw, _ = _flow_arg(who + ": flow_bw", flow_bw, "[2,H,W] or [N,2,H,W]")
+    if fw.shape != bw.shape or fw.device != bw.device:
+        raise DvsError("%s: flow_fw %s on %s, flow_bw %s on %s" % (who, tuple(fw.shape), fw.device, tuple(bw.shape), bw.device))
+    alpha, beta = float(alpha), float(beta)
+    if not (0.0 <= alpha < float("inf") and 0.0 <= beta < float("inf")):
+        raise DvsError("%s: alpha=%r, beta=%r must be finite and not negative" % (who, alpha, beta))
+    fw, fw_image, fw_plane, fw_row = _rows(fw)
+    bw, bw_image, bw_plane, bw_row = _rows(bw)
+    N, _, H, W = fw.shape
+    valid = torch.empty((2, N, H, W), device=fw.device, dtype=torch.uint8)
+    over = torch.empty((2, N, H, W), device=fw.device, dtype=torch.float32) if excess else None
+    p = lambda t, i: t[i].data_ptr() if t is not None else None
+    check(_lib.lib().dvs_flow_consistency(fw.data_ptr(), fw_image, fw_plane, fw_row, bw.data_ptr(), bw_image, bw_plane, bw_row,
+                                          p(valid, 0), p(valid, 1), p(over, 0), p(over, 1), N, H, W, alpha, beta, _lib.stream()),
+          "dvs_flow_consistency")
+    out = (valid[0], valid[1]) + ((over[0], over[1]) if excess else ())
+    return out if batched else tuple(t[0] for t in out)
 
 
 class InputPadder:
@@ -218,10 +266,14 @@ class FlowFrame:
     """What FlowStream.push returns for a pair: flow_low [N,2,Hp/8,Wp/8] at the padded size, flow_up [N,2,H,W] (a view of the padded
     flow), image uint8 [N,H,W,3] or None, all on the device.  With host=True, image_host and flow_low_host are numpy views of
     pinned host memory that is filled asynchronously: reading one waits for this frame's copy event first (`wait()`), and the
-    views stay valid until the push after next (two buffers)."""
+    views stay valid until the push after next (two buffers).
+    A bidirectional stream also fills flow_low_bw and flow_up_bw (the pair current -> previous, shaped like flow_low and flow_up),
+    valid uint8 [N,H,W] on the previous frame's grid and valid_bw on the current frame's (flow_consistency of flow_up and
+    flow_up_bw), and with host=True valid_host; they are None otherwise.  flow_low, flow_up and image are the forward pair's."""
 
-    def __init__(self, flow_low, flow_up, image, slot=None):
+    def __init__(self, flow_low, flow_up, image, slot=None, flow_low_bw=None, flow_up_bw=None, valid=None, valid_bw=None):
         self.flow_low, self.flow_up, self.image, self._slot = flow_low, flow_up, image, slot
+        self.flow_low_bw, self.flow_up_bw, self.valid, self.valid_bw = flow_low_bw, flow_up_bw, valid, valid_bw
 
     def wait(self):
         if self._slot is None:
@@ -237,6 +289,11 @@ class FlowFrame:
     def image_host(self):
         image = self.wait()._slot["image"]
         return image.numpy() if image is not None else None
+
+    @property
+    def valid_host(self):
+        valid = self.wait()._slot["valid"]
+        return valid.numpy() if valid is not None else None
 
 
 class FlowStream:
@@ -264,10 +321,14 @@ class FlowStream:
     of a shape.  The returned tensors are then the graph's static outputs: consume (or clone) them before the next push.  A zeroed
     flow_init is the cold start, so reset() zeroes the buffer and marks the slot empty without a new capture; the graph is
     captured again by itself when the weights or the BatchNorm buffers changed (stale()).
-    host=True: the picture and flow_low are also copied asynchronously into two alternating pinned host buffers (FlowFrame)."""
+    host=True: the picture and flow_low are also copied asynchronously into two alternating pinned host buffers (FlowFrame).
+    bidirectional=True: each pair is model.refine_pair(previous, current), ONE loop at batch 2N (rows 0 .. N-1 previous -> current,
+    rows N .. 2N-1 current -> previous; no further encoder pass), the kept flow is forward_interpolate of all 2N flow_low, and
+    flow_consistency(flow_up, flow_up_bw, fb_alpha, fb_beta) on the un-padded views adds the two validity masks, inside the same
+    graph.  The default changes nothing.  Measured: DESIGN.md section 23."""
 
     def __init__(self, model, iters=12, warm_start=True, pad_mode="sintel", image=True, convert_to_bgr=False, bgr=False,
-                 graph=True, host=False, warmup=2):
+                 graph=True, host=False, warmup=2, bidirectional=False, fb_alpha=0.01, fb_beta=0.5):
         if not isinstance(model, (RAFT, SmallRAFT)):
             raise DvsError("FlowStream: model must be a raft.RAFT or a raft.SmallRAFT, got %s" % type(model).__name__)
         if int(iters) < 1:
@@ -275,6 +336,9 @@ class FlowStream:
         self.model, self.iters, self.warm_start, self.pad_mode = model, int(iters), bool(warm_start), pad_mode
         self.image, self.convert_to_bgr, self.bgr = bool(image), bool(convert_to_bgr), bool(bgr)
         self.use_graph, self.host, self.warmup = bool(graph), bool(host), int(warmup)
+        self.bidirectional, self.fb_alpha, self.fb_beta = bool(bidirectional), float(fb_alpha), float(fb_beta)
+        if not (0.0 <= self.fb_alpha < float("inf") and 0.0 <= self.fb_beta < float("inf")):
+            raise DvsError("FlowStream: fb_alpha=%r, fb_beta=%r must be finite and not negative" % (fb_alpha, fb_beta))
         self.flow_init = None               # eager: the kept flow or None; graph: the persistent buffer
         self._prev, self._shape = None, None  # the previous frame's features (graph: the slot, with _have_prev)
         self._have_prev = False
@@ -293,30 +357,37 @@ class FlowStream:
     # ---- one step, eager or under capture --------------------------------------------------------------------------------------
     def _refine(self, prev, feat, flow_init):
         """(flow_low, flow_up at the padded size): RAFT has a test mode; SmallRAFT's counterpart is last_only and its flow_low."""
+        refine = self.model.refine_pair if self.bidirectional else self.model.refine     # refine_pair: batch 2N, forward rows first
         if isinstance(self.model, RAFT):
-            return self.model.refine(prev, feat, iters=self.iters, flow_init=flow_init, test_mode=True)
-        up = self.model.refine(prev, feat, iters=self.iters, flow_init=flow_init, last_only=True)[-1]
+            return refine(prev, feat, iters=self.iters, flow_init=flow_init, test_mode=True)
+        up = refine(prev, feat, iters=self.iters, flow_init=flow_init, last_only=True)[-1]
         return self.model.flow_low[-1], up
 
     def _encode(self, frames, padder):
         return self.model.encode_frame(frame_ingest(frames, padder._pad, self.bgr))
 
     def _pair(self, prev, feat, flow_init, padder):
+        """(FlowFrame's fields in the order of its arguments, without the slot; the next flow_init)."""
         flow_low, flow_pad = self._refine(prev, feat, flow_init)
         kept = forward_interpolate(flow_low) if self.warm_start else None
         flow_up = padder.unpad(flow_pad)
+        both = ()
+        if self.bidirectional:                              # the mask is taken on the un-padded views: the padding is not the image
+            N = flow_up.shape[0] // 2
+            both = (flow_low[N:], flow_up[N:]) + flow_consistency(flow_up[:N], flow_up[N:], self.fb_alpha, self.fb_beta)
+            flow_low, flow_up = flow_low[:N], flow_up[:N]
         image = flow_to_image(flow_up, convert_to_bgr=self.convert_to_bgr) if self.image else None
-        return flow_low, flow_up, image, kept
+        return (flow_low, flow_up, image) + both, kept
 
     def _graph_step(self, padder):
         """What the graph holds: s_frame -> outputs, flow_init and the previous slot advanced in place."""
         feat = self._encode(self.s_frame, padder)
-        flow_low, flow_up, image, kept = self._pair(self._prev, feat, self.flow_init, padder)
+        out, kept = self._pair(self._prev, feat, self.flow_init, padder)
         if kept is not None:
             self.flow_init.copy_(kept)
         for name in ("fmap", "net", "inp"):                 # copy_ bumps inp's version: the update block's hoisted terms are re-made
             getattr(self._prev, name).copy_(getattr(feat, name))
-        return flow_low, flow_up, image
+        return out
 
     # ---- capture -----------------------------------------------------------------------------------------------------------------
     def _derived(self):
@@ -334,7 +405,8 @@ class FlowStream:
                 feat = self._encode(self.s_frame, padder)   # a padded size the model refuses: the model's own error
             self._prev = SimpleNamespace(fmap=feat.fmap.clone(), net=feat.net.clone(), inp=feat.inp.clone())
             N, _, h, w = feat.fmap.shape
-            self.flow_init = torch.zeros((N, 2, h, w), device=frames.device) if self.warm_start else None
+            pairs = 2 * N if self.bidirectional else N      # bidirectional: the kept flow of both directions, forward rows first
+            self.flow_init = torch.zeros((pairs, 2, h, w), device=frames.device) if self.warm_start else None
         state = [t.clone() for t in self._state()]
         side = torch.cuda.Stream(device=frames.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -396,16 +468,15 @@ class FlowStream:
         slot = None
         if self.host:
             slot = self._host_slot(out)
-        return FlowFrame(out[0], out[1], out[2], slot)
+        return FlowFrame(out[0], out[1], out[2], slot, *out[3:])
 
     def _push_eager(self, frames, padder):
         feat = self._encode(frames, padder)                 # a padded size the model refuses: the model's own error
         prev, self._prev = self._prev, feat
         if prev is None:
             return None
-        flow_low, flow_up, image, kept = self._pair(prev, feat, self.flow_init, padder)
-        self.flow_init = kept
-        return flow_low, flow_up, image
+        out, self.flow_init = self._pair(prev, feat, self.flow_init, padder)
+        return out
 
     def _push_graph(self, frames, padder):
         if self.graph is None or self._graph_shape != self._shape_of(frames):
@@ -423,14 +494,17 @@ class FlowStream:
         return None
 
     def _host_slot(self, out):
+        valid = out[5] if self.bidirectional else None
         if self._slots is None or self._slots[0]["flow_low"].shape != out[0].shape or (
                 out[2] is not None and self._slots[0]["image"].shape != out[2].shape):
             pin = lambda t: torch.zeros(tuple(t.shape), dtype=t.dtype, pin_memory=True) if t is not None else None
-            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), event=torch.cuda.Event()) for _ in range(2)]
+            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), valid=pin(valid), event=torch.cuda.Event()) for _ in range(2)]
         slot = self._slots[self._n & 1]
         self._n += 1
         slot["flow_low"].copy_(out[0], non_blocking=True)
         if out[2] is not None:
             slot["image"].copy_(out[2], non_blocking=True)
+        if valid is not None:
+            slot["valid"].copy_(valid, non_blocking=True)
         slot["event"].record()
         return slot

@@ -913,6 +913,43 @@ int dvs_flow_to_image(const float* flow, long long plane_stride, long long row_s
 int dvs_frame_ingest(const unsigned char* src, long long image_stride, long long row_stride, float* dst, int N, int H, int W,
                      int left, int right, int top, int bottom, int bgr, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Forward-backward consistency of two flows: a validity / occlusion mask per pixel
+ *     the criterion of UnFlow (Meister et al. 2018, eq. 2): |w_f + w_b(x + w_f)|^2 < alpha (|w_f|^2 + |w_b(x + w_f)|^2) + beta;
+ *     the gather is bilinear_sampler (model/raft/core/utils/utils.py:57-71) in pixel coordinates, without its normalise round trip;
+ *     replaces a grid_sample and half a dozen elementwise launches per frame
+ *
+ *   a, b: fp32 flows of N images of H x W pixels, a on image 1's grid and b on image 2's; u of pixel (n, y, x) of a at
+ *   a[n * a_image_stride + y * a_row_stride + x] and v one a_plane_stride further (element strides; b alike), so the un-padded view
+ *   of a padded [N][2][Hp][Wp] flow is read in place.  valid_a, valid_b: uint8 [N][H][W]; excess_a, excess_b: fp32 [N][H][W]; all
+ *   dense, each may be NULL (all four NULL: nothing is launched).  One launch computes both directions; for pixel (x, y) of
+ *   direction a, in fp32, every operation rounded on its own (no contraction), in exactly this order:
+ *       qx = float(x) + a.u(x,y)          qy = float(y) + a.v(x,y)
+ *       inside = 0 <= qx <= W-1  and  0 <= qy <= H-1          (closed; false for NaN)
+ *       x0 = floor(qx), y0 = floor(qy), wx = qx - x0, wy = qy - y0, x1 = min(x0+1, W-1), y1 = min(y0+1, H-1)
+ *       s(p) = (p[y0,x0]*(1-wx) + p[y0,x1]*wx)*(1-wy) + (p[y1,x0]*(1-wx) + p[y1,x1]*wx)*wy      for p = b.u, b.v  ->  bu, bv
+ *       sx = a.u + bu, sy = a.v + bv
+ *       d   = sx*sx + sy*sy
+ *       m   = (a.u*a.u + a.v*a.v) + (bu*bu + bv*bv)
+ *       thr = alpha*m + beta
+ *       excess = d - thr                  (+inf where not inside, and where d - thr is NaN: a non-finite sample of b)
+ *       valid  = inside and excess <= 0
+ *   Direction b is the same arithmetic with the roles swapped.  The border is closed: a zero flow is valid on the whole image; a
+ *   clamped tap carries weight 0 and a pixel that is not inside reads nothing of its partner, so nothing outside the two views is
+ *   read.  A lane owns four consecutive pixels of a row: two 16-byte loads, one dword of mask bytes and one 16-byte store of excess
+ *   where W, all six strides and every pointer allow, single elements otherwise.  No atomics, no workspace, no LDS; every output
+ *   element is written once: the result repeats bit for bit, does not depend on the launch geometry, and an image's result does
+ *   not depend on the other images of the batch.
+ *   1 <= N <= 65535, 1 <= H, W <= 2^24, H * ceil(W / 4) < 2^31 - 256, row stride >= W, plane stride >= (H - 1) * row stride + W,
+ *   image stride >= plane stride + (H - 1) * row stride + W, alpha and beta finite and >= 0; 4-byte aligned pointers; the outputs
+ *   must not overlap the flows.  DVS_ERR_INVALID, before any launch, otherwise.
+ *   dvs_set_precision does not affect this entry.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_flow_consistency(const float* a, long long a_image_stride, long long a_plane_stride, long long a_row_stride, const float* b,
+                         long long b_image_stride, long long b_plane_stride, long long b_row_stride, unsigned char* valid_a,
+                         unsigned char* valid_b, float* excess_a, float* excess_b, int N, int H, int W, float alpha, float beta,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
