@@ -196,6 +196,8 @@ _SIGNATURES = {
     "dvs_flow_to_image": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp]),
     "dvs_frame_ingest": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp] + [C.c_int] * 8 + [_vp]),
     "dvs_flow_consistency": (C.c_int, ([_vp] + [C.c_longlong] * 3) * 2 + [_vp] * 4 + [C.c_int] * 3 + [C.c_float, C.c_float, _vp]),
+    "dvs_rigid_flow": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp] + [C.c_longlong] * 3 + [_vp] * 4 + [C.c_int] * 3
+                       + [C.c_float] * 3 + [_vp]),
 }
 
 _lib = None

@@ -9,6 +9,9 @@
                                    graph=True replays it as one HIP graph, host=True adds pinned host copies, bidirectional=True
                                    runs both directions as one loop at batch 2N and adds the two consistency masks
     flow_consistency(fw, bw, ...)  csrc/flowcons.hip: the forward-backward check of UnFlow, both validity masks by one launch
+    rigid_flow(depth, T, K, ...)   csrc/rigidflow.hip: the flow a static scene shows under a depth map and a camera motion, and a
+                                   static / moving label for a measured flow against it, by one launch
+    RigidFlowStream(model, ...)    FlowStream whose push also takes depth, T, K, inv_K and adds rigid and motion to every pair
 
     pred = FlowPredictor(raft.RAFT({"small": False}).cuda().eval(), iters=12)
     for frame1, frame2 in pairs:                       # [B,3,H,W] fp32 in 0 .. 1 on the GPU, any H, W the padded model accepts
@@ -136,6 +139,91 @@ def flow_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5, excess=False):
           "dvs_flow_consistency")
     out = (valid[0], valid[1]) + ((over[0], over[1]) if excess else ())
     return out if batched else tuple(t[0] for t in out)
+
+
+def _planes(d):
+    """(tensor, image stride, row stride) in elements with which dvs_rigid_flow reads the depth `d` [N,H,W]: `d` itself where its
+    rows are dense and rows and images do not overlap (the policy of _rows), else ONE dense copy."""
+    N, H, W = d.shape
+    s0, s1, s2 = d.stride()
+    row = s1 if H > 1 else W
+    extent = (H - 1) * row + W
+    image = s0 if N > 1 else extent
+    if (s2 == 1 or W == 1) and row >= W and image >= extent:
+        return d, image, row
+    return d.contiguous(), H * W, W
+
+
+def _matrix_arg(who, m, N, single):
+    """Refuse `m` unless it is an fp32 GPU [N,4,4] (or, with `single`, a [4,4] that stands for every image)."""
+    want = "[%d,4,4]%s expected" % (N, " or [4,4]" if single else "")
+    gpu_arg(who, m, want, rank=(2, 3) if single else 3, ok=lambda shape: tuple(shape) in ((N, 4, 4),) + (((4, 4),) if single else ()))
+
+
+def _rigid_args(who, depth, T, K, inv_K, flow=None, valid=None, shape=None):
+    """The argument checks of rigid_flow, made on the tensors' descriptions alone (before any launch or copy); `shape`: the
+    (N, H, W) the caller demands.  Returns (N, H, W)."""
+    gpu_arg(who + ": depth", depth, "[N,1,H,W] or [N,H,W] expected", rank=(3, 4),
+            ok=lambda s: min(s) >= 1 and (len(s) == 3 or s[1] == 1) and (shape is None or (s[0], s[-2], s[-1]) == tuple(shape)))
+    N, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
+    _matrix_arg(who + ": T", T, N, False)
+    _matrix_arg(who + ": K", K, N, True)
+    if inv_K is not None:
+        _matrix_arg(who + ": inv_K", inv_K, N, True)
+    if flow is not None:
+        gpu_arg(who + ": flow", flow, "[%d,2,%d,%d] expected" % (N, H, W), ok=lambda s: tuple(s) == (N, 2, H, W))
+    if valid is not None:
+        if not torch.is_tensor(valid) or not valid.is_cuda:
+            raise DvsError("%s: valid: GPU tensors only (got %s); this package has no CPU path" % (who, getattr(valid, "device", type(valid))))
+        if valid.dtype != torch.uint8 or tuple(valid.shape) != (N, H, W):
+            raise DvsError("%s: valid: uint8 [%d,%d,%d] expected (the mask of flow_consistency), got %s %s"
+                           % (who, N, H, W, valid.dtype, tuple(valid.shape)))
+    for name, t in (("T", T), ("K", K), ("inv_K", inv_K), ("flow", flow), ("valid", valid)):
+        if t is not None and t.device != depth.device:
+            raise DvsError("%s: %s is on %s, depth on %s" % (who, name, t.device, depth.device))
+    return N, H, W
+
+
+def rigid_flow(depth, T, K, inv_K=None, flow=None, valid=None, alpha=0.01, beta=0.5, eps=1e-7, excess=False):
+    """The flow a STATIC scene shows under this depth and this camera motion, and where a measured flow disagrees with it, on the
+    device in ONE launch (dvs_rigid_flow; include/dvslam.h states the arithmetic): the reference's BackprojectDepth and Project3D
+    (vo/learner_func.py:106-159) in pixel coordinates, rigid = project(K T backproject(depth, inv_K)) - (x, y).
+
+    depth [N,1,H,W] or [N,H,W] fp32, of the flow's SOURCE frame; T [N,4,4] maps points of that camera into the target camera;
+    K and inv_K [4,4] or [N,4,4] (the reference's 4x4 intrinsics).  inv_K=None inverts K once with torch.linalg.inv on the device:
+    the bit-for-bit contract of the entry holds for an inv_K that the caller passes.  Returns rigid fp32 [N,2,H,W].
+    With flow [N,2,H,W] (and optionally valid uint8 [N,H,W], the mask of flow_consistency): (rigid, label), label uint8 [N,H,W] =
+    0 not judged (the pixel projects outside the image or behind the camera, valid is 0, or a value is not finite), 1 static
+
+        |flow - rigid|^2 <= alpha * (|flow|^2 + |rigid|^2) + beta
+
+    2 moving (or wrong depth).  excess=True: (rigid, label, excess), the fp32 field `left side - right side` (+inf where label is
+    0).  valid is read with a flow only.  Views whose rows are dense (InputPadder.unpad's, a batch slice) are read in place through
+    their strides; any other layout is copied once."""
+    who = "rigid_flow"
+    N, H, W = _rigid_args(who, depth, T, K, inv_K, flow, valid)
+    alpha, beta, eps = float(alpha), float(beta), float(eps)
+    inf = float("inf")
+    if not (0.0 <= alpha < inf and 0.0 <= beta < inf and 0.0 <= eps < inf):
+        raise DvsError("%s: alpha=%r, beta=%r, eps=%r must be finite and not negative" % (who, alpha, beta, eps))
+    if excess and flow is None:
+        raise DvsError("%s: excess=True needs a flow" % who)
+    d, d_image, d_row = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
+    mat = lambda m: m.detach().expand(N, 4, 4).contiguous()
+    T, K = mat(T), mat(K)
+    inv_K = mat(inv_K) if inv_K is not None else torch.linalg.inv(K).contiguous()
+    f, f_image, f_plane, f_row = _rows(flow.detach()) if flow is not None else (None, 0, 0, 0)
+    valid = valid.contiguous() if valid is not None else None
+    rigid = torch.empty((N, 2, H, W), device=d.device, dtype=torch.float32)
+    label = torch.empty((N, H, W), device=d.device, dtype=torch.uint8) if f is not None else None
+    over = torch.empty((N, H, W), device=d.device, dtype=torch.float32) if excess else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    check(_lib.lib().dvs_rigid_flow(d.data_ptr(), d_image, d_row, K.data_ptr(), inv_K.data_ptr(), T.data_ptr(), p(f), f_image, f_plane,
+                                    f_row, p(valid), rigid.data_ptr(), p(over), p(label), N, H, W, alpha, beta, eps, _lib.stream()),
+          "dvs_rigid_flow")
+    if f is None:
+        return rigid
+    return (rigid, label, over) if excess else (rigid, label)
 
 
 class InputPadder:
@@ -269,11 +357,15 @@ class FlowFrame:
     views stay valid until the push after next (two buffers).
     A bidirectional stream also fills flow_low_bw and flow_up_bw (the pair current -> previous, shaped like flow_low and flow_up),
     valid uint8 [N,H,W] on the previous frame's grid and valid_bw on the current frame's (flow_consistency of flow_up and
-    flow_up_bw), and with host=True valid_host; they are None otherwise.  flow_low, flow_up and image are the forward pair's."""
+    flow_up_bw), and with host=True valid_host; they are None otherwise.  flow_low, flow_up and image are the forward pair's.
+    A rigid stream (RigidFlowStream) also fills rigid fp32 [N,2,H,W] and motion uint8 [N,H,W] (rigid_flow's rigid and label for
+    flow_up), and with host=True motion_host; they are None otherwise."""
 
-    def __init__(self, flow_low, flow_up, image, slot=None, flow_low_bw=None, flow_up_bw=None, valid=None, valid_bw=None):
+    def __init__(self, flow_low, flow_up, image, slot=None, flow_low_bw=None, flow_up_bw=None, valid=None, valid_bw=None,
+                 rigid=None, motion=None):
         self.flow_low, self.flow_up, self.image, self._slot = flow_low, flow_up, image, slot
         self.flow_low_bw, self.flow_up_bw, self.valid, self.valid_bw = flow_low_bw, flow_up_bw, valid, valid_bw
+        self.rigid, self.motion = rigid, motion
 
     def wait(self):
         if self._slot is None:
@@ -294,6 +386,11 @@ class FlowFrame:
     def valid_host(self):
         valid = self.wait()._slot["valid"]
         return valid.numpy() if valid is not None else None
+
+    @property
+    def motion_host(self):
+        motion = self.wait()._slot.get("motion")
+        return motion.numpy() if motion is not None else None
 
 
 class FlowStream:
@@ -325,7 +422,9 @@ class FlowStream:
     bidirectional=True: each pair is model.refine_pair(previous, current), ONE loop at batch 2N (rows 0 .. N-1 previous -> current,
     rows N .. 2N-1 current -> previous; no further encoder pass), the kept flow is forward_interpolate of all 2N flow_low, and
     flow_consistency(flow_up, flow_up_bw, fb_alpha, fb_beta) on the un-padded views adds the two validity masks, inside the same
-    graph.  The default changes nothing.  Measured: DESIGN.md section 23."""
+    graph.  The default changes nothing.  Measured: DESIGN.md section 23.
+    The rigid mode (rigid flow from depth and pose, and a moving-object label per pixel) is RigidFlowStream, below: this
+    constructor's signature stays as it is."""
 
     def __init__(self, model, iters=12, warm_start=True, pad_mode="sintel", image=True, convert_to_bgr=False, bgr=False,
                  graph=True, host=False, warmup=2, bidirectional=False, fb_alpha=0.01, fb_beta=0.5):
@@ -345,6 +444,8 @@ class FlowStream:
         self.graph, self._graph_shape = None, None
         self._slots, self._n = None, 0
         self.frame_copied = None            # the event behind the last host frame's H2D copy
+        self.rigid, self.rigid_alpha, self.rigid_beta = False, 0.01, 0.5      # RigidFlowStream's mode
+        self._geo = None                    # graph mode: the static depth, T, K and inv_K the rigid-flow node reads
 
     def reset(self):
         """A new sequence: the next push encodes its frame and returns None."""
@@ -366,8 +467,9 @@ class FlowStream:
     def _encode(self, frames, padder):
         return self.model.encode_frame(frame_ingest(frames, padder._pad, self.bgr))
 
-    def _pair(self, prev, feat, flow_init, padder):
-        """(FlowFrame's fields in the order of its arguments, without the slot; the next flow_init)."""
+    def _pair(self, prev, feat, flow_init, padder, geo=None):
+        """(FlowFrame's fields in the order of its arguments, without the slot; the next flow_init).  geo: a rigid stream's
+        (depth, T, K, inv_K)."""
         flow_low, flow_pad = self._refine(prev, feat, flow_init)
         kept = forward_interpolate(flow_low) if self.warm_start else None
         flow_up = padder.unpad(flow_pad)
@@ -377,12 +479,15 @@ class FlowStream:
             both = (flow_low[N:], flow_up[N:]) + flow_consistency(flow_up[:N], flow_up[N:], self.fb_alpha, self.fb_beta)
             flow_low, flow_up = flow_low[:N], flow_up[:N]
         image = flow_to_image(flow_up, convert_to_bgr=self.convert_to_bgr) if self.image else None
+        if self.rigid:                                      # on the same un-padded view, masked by the forward validity
+            both = (both or (None,) * 4) + rigid_flow(*geo, flow=flow_up, valid=both[2] if both else None, alpha=self.rigid_alpha,
+                                                      beta=self.rigid_beta)
         return (flow_low, flow_up, image) + both, kept
 
     def _graph_step(self, padder):
         """What the graph holds: s_frame -> outputs, flow_init and the previous slot advanced in place."""
         feat = self._encode(self.s_frame, padder)
-        out, kept = self._pair(self._prev, feat, self.flow_init, padder)
+        out, kept = self._pair(self._prev, feat, self.flow_init, padder, self._geo)
         if kept is not None:
             self.flow_init.copy_(kept)
         for name in ("fmap", "net", "inp"):                 # copy_ bumps inp's version: the update block's hoisted terms are re-made
@@ -407,6 +512,10 @@ class FlowStream:
             N, _, h, w = feat.fmap.shape
             pairs = 2 * N if self.bidirectional else N      # bidirectional: the kept flow of both directions, forward rows first
             self.flow_init = torch.zeros((pairs, 2, h, w), device=frames.device) if self.warm_start else None
+            if self.rigid:                                  # filled before every replay, as s_frame is
+                f32 = dict(device=frames.device, dtype=torch.float32)
+                self._geo = (torch.ones((N,) + tuple(frames.shape[1:3]), **f32),) + tuple(
+                    torch.eye(4, **f32).repeat(N, 1, 1) for _ in range(3))
         state = [t.clone() for t in self._state()]
         side = torch.cuda.Stream(device=frames.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -440,7 +549,7 @@ class FlowStream:
 
     # ---- push --------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def push(self, frame):
+    def push(self, frame, depth=None, T=None, K=None, inv_K=None):
         if self.model.training:
             raise DvsError("FlowStream: the model is in train() mode; call model.eval() (inference runs BatchNorm on its running "
                            "statistics and keeps no graph)")
@@ -457,11 +566,12 @@ class FlowStream:
         if self._shape is not None and shape != self._shape:
             raise DvsError("FlowStream: input changed from %s on %s to %s on %s inside a sequence; call reset() first"
                            % (self._shape + shape))
+        geo = self._geo_args(frames, depth, T, K, inv_K)
         padder = InputPadder(frames.shape[1:3], self.pad_mode)
         if self.use_graph:
-            out = self._push_graph(frames, padder)
+            out = self._push_graph(frames, padder, geo)
         else:
-            out = self._push_eager(frames, padder)
+            out = self._push_eager(frames, padder, geo)
         self._shape = shape
         if out is None:
             return None
@@ -470,21 +580,44 @@ class FlowStream:
             slot = self._host_slot(out)
         return FlowFrame(out[0], out[1], out[2], slot, *out[3:])
 
-    def _push_eager(self, frames, padder):
+    def _geo_args(self, frames, depth, T, K, inv_K):
+        """A rigid stream's (depth, T, K, inv_K) for the pair this push completes, checked; None for the first frame of a
+        sequence (no pair: the arguments are not read) and for a stream that is not rigid."""
+        if not self.rigid:
+            if not (depth is None and T is None and K is None and inv_K is None):
+                raise DvsError("FlowStream: depth, T, K and inv_K are arguments of a rigid stream (RigidFlowStream)")
+            return None
+        if self._shape is None:
+            return None
+        for name, t in (("depth", depth), ("T", T), ("K", K)):
+            if t is None:
+                raise DvsError("FlowStream: a rigid stream needs %s with every frame after the first (depth: of the PREVIOUS frame, "
+                               "T: previous -> current camera, K: the 4x4 intrinsics)" % name)
+        N, H, W = frames.shape[:3]
+        _rigid_args("FlowStream", depth, T, K, inv_K, shape=(N, H, W))
+        if depth.device != frames.device:
+            raise DvsError("FlowStream: depth is on %s, the frame on %s" % (depth.device, frames.device))
+        depth = depth.detach() if depth.dim() == 3 else depth.detach()[:, 0]
+        return depth, T, K, inv_K if inv_K is not None else torch.linalg.inv(K)
+
+    def _push_eager(self, frames, padder, geo=None):
         feat = self._encode(frames, padder)                 # a padded size the model refuses: the model's own error
         prev, self._prev = self._prev, feat
         if prev is None:
             return None
-        out, self.flow_init = self._pair(prev, feat, self.flow_init, padder)
+        out, self.flow_init = self._pair(prev, feat, self.flow_init, padder, geo)
         return out
 
-    def _push_graph(self, frames, padder):
+    def _push_graph(self, frames, padder, geo=None):
         if self.graph is None or self._graph_shape != self._shape_of(frames):
             self._have_prev = False
             self._capture(frames, padder)
         elif self.stale():
             self._capture(frames, padder)
         self.s_frame.copy_(frames, non_blocking=True)
+        if geo is not None:
+            for static, t in zip(self._geo, geo):           # a [4,4] K or inv_K is broadcast over the images
+                static.copy_(t, non_blocking=True)
         self.graph.replay()
         if self._have_prev:
             return self.static_out
@@ -495,10 +628,12 @@ class FlowStream:
 
     def _host_slot(self, out):
         valid = out[5] if self.bidirectional else None
+        motion = out[8] if self.rigid else None
         if self._slots is None or self._slots[0]["flow_low"].shape != out[0].shape or (
                 out[2] is not None and self._slots[0]["image"].shape != out[2].shape):
             pin = lambda t: torch.zeros(tuple(t.shape), dtype=t.dtype, pin_memory=True) if t is not None else None
-            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), valid=pin(valid), event=torch.cuda.Event()) for _ in range(2)]
+            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), valid=pin(valid), motion=pin(motion), event=torch.cuda.Event())
+                           for _ in range(2)]
         slot = self._slots[self._n & 1]
         self._n += 1
         slot["flow_low"].copy_(out[0], non_blocking=True)
@@ -506,5 +641,30 @@ class FlowStream:
             slot["image"].copy_(out[2], non_blocking=True)
         if valid is not None:
             slot["valid"].copy_(valid, non_blocking=True)
+        if motion is not None:
+            slot["motion"].copy_(motion, non_blocking=True)
         slot["event"].record()
         return slot
+
+
+class RigidFlowStream(FlowStream):
+    """FlowStream in its rigid mode: every pair also gets the flow a static scene would show under the previous frame's depth and
+    the camera motion, and a label per pixel that says where the measured flow disagrees with it (rigid_flow, dvs_rigid_flow).
+
+        stream = RigidFlowStream(model, iters=12, bidirectional=True)       # every FlowStream argument, plus rigid_alpha, rigid_beta
+        for frame in frames:
+            r = stream.push(frame, depth=depth_prev, T=T, K=K, inv_K=inv_K) # depth of the PREVIOUS frame, T: previous -> current
+            # r.rigid [N,2,H,W], r.motion uint8 [N,H,W]: 0 not judged, 1 static, 2 moving; host=True: r.motion_host
+
+    depth [N,1,H,W] or [N,H,W] at the un-padded frame size, T [N,4,4], K and inv_K [4,4] or [N,4,4], fp32 on the frame's device;
+    inv_K=None inverts K with torch.linalg.inv on every push.  The first frame of a sequence completes no pair and reads none of
+    them; after it a missing or mis-shaped one is a DvsError that names it.  The kernel runs on the un-padded flow_up view, with
+    `valid` as its mask in a bidirectional stream (an occluded pixel is not judged).  graph=True: the four tensors are copied into
+    static buffers before the replay, as the frame is, and the kernel is a node of the same single-stream graph; reset(), stale()
+    and the re-capture rules are FlowStream's.  rigid=False is a plain FlowStream.  Measured: DESIGN.md section 24."""
+
+    def __init__(self, model, *args, rigid=True, rigid_alpha=0.01, rigid_beta=0.5, **kw):
+        super().__init__(model, *args, **kw)
+        self.rigid, self.rigid_alpha, self.rigid_beta = bool(rigid), float(rigid_alpha), float(rigid_beta)
+        if not (0.0 <= self.rigid_alpha < float("inf") and 0.0 <= self.rigid_beta < float("inf")):
+            raise DvsError("FlowStream: rigid_alpha=%r, rigid_beta=%r must be finite and not negative" % (rigid_alpha, rigid_beta))

@@ -950,6 +950,51 @@ int dvs_flow_consistency(const float* a, long long a_image_stride, long long a_p
                          unsigned char* valid_b, float* excess_a, float* excess_b, int N, int H, int W, float alpha, float beta,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Rigid flow from depth and pose, and a moving-object label for a measured flow
+ *     the flow a static scene shows under this depth and this camera motion: the reference's BackprojectDepth and Project3D
+ *     (vo/learner_func.py:106-159) in pixel coordinates, without the normalise round trip; the residual of a measured flow
+ *     against it (GeoNet, Yin and Shi 2018) with the threshold form of dvs_flow_consistency;
+ *     replaces two batched matmuls, a divide, a grid and half a dozen elementwise launches per frame
+ *
+ *   depth: fp32, N images of H x W pixels, d of pixel (n, y, x) at depth[n * depth_image_stride + y * depth_row_stride + x]
+ *   (element strides).  K, inv_K, T: fp32 [N][4][4], dense, the reference's conventions; T maps points of the flow's SOURCE
+ *   camera (the one depth belongs to) into the target camera.  flow (optional): fp32, u of pixel (n, y, x) at
+ *   flow[n * flow_image_stride + y * flow_row_stride + x] and v one flow_plane_stride further, so the un-padded view of a padded
+ *   [N][2][Hp][Wp] flow is read in place.  valid (optional, read with a flow only): uint8 [N][H][W], dense, the mask of
+ *   dvs_flow_consistency.  rigid: fp32 [N][2][H][W]; excess: fp32 [N][H][W]; label: uint8 [N][H][W]; all dense, each may be NULL
+ *   (all three NULL: nothing is launched); excess and label need a flow.  In fp32, every operation rounded on its own (no
+ *   contraction), in exactly this order, iK = inv_K:
+ *     per image:
+ *       P[i][j] = ((K[i][0]*T[0][j] + K[i][1]*T[1][j]) + K[i][2]*T[2][j]) + K[i][3]*T[3][j]          i < 3
+ *     per pixel (x, y), d = depth:
+ *       rx = (iK[0][0]*x + iK[0][1]*y) + iK[0][2]                ry, rz: rows 1, 2
+ *       X = d*rx, Y = d*ry, Z = d*rz
+ *       cx = ((P[0][0]*X + P[0][1]*Y) + P[0][2]*Z) + P[0][3]     cy, cz: rows 1, 2
+ *       den = cz + eps
+ *       px = cx / den, py = cy / den                             (the correctly rounded quotient, not a reciprocal)
+ *       ru = px - x, rv = py - y                                 (rigid; a non-finite component is stored as the quiet NaN 0x7FC00000)
+ *       inside = cz > 0 and 0 <= px <= W-1 and 0 <= py <= H-1    (closed; false for NaN)
+ *     with flow = (fu, fv):
+ *       ex = fu - ru, ey = fv - rv, e2 = ex*ex + ey*ey
+ *       m   = (fu*fu + fv*fv) + (ru*ru + rv*rv)
+ *       thr = alpha*m + beta
+ *       excess = e2 - thr                 (+inf where not inside, where valid is given and 0, and where e2 - thr is NaN)
+ *       label  = 0 (not judged) where excess is +inf by that rule, 1 (static) where excess <= 0, 2 (moving) otherwise
+ *   P is computed by every lane from uniform loads: one launch, no workspace.  A lane owns four consecutive pixels of a row:
+ *   16-byte loads of depth and flow, 16-byte stores of rigid and excess and one dword of label bytes where W, every stride and
+ *   every pointer allow, single elements otherwise.  No atomics, no LDS; every output element is written once: the result repeats
+ *   bit for bit, does not depend on the launch geometry, and an image's result does not depend on the other images of the batch.
+ *   1 <= N <= 65535, 1 <= H, W <= 2^24, H * ceil(W / 4) < 2^31 - 256, row strides >= W, depth image stride >= (H - 1) * row stride + W,
+ *   flow plane stride >= (H - 1) * row stride + W, flow image stride >= plane stride + (H - 1) * row stride + W, alpha, beta and eps
+ *   finite and >= 0; 4-byte aligned fp32 pointers; no output may overlap an input.  DVS_ERR_INVALID, before any launch, otherwise.
+ *   Only `stream` is used; dvs_set_precision does not affect this entry.
+ * ------------------------------------------------------------------------------------------- */
+int dvs_rigid_flow(const float* depth, long long depth_image_stride, long long depth_row_stride, const float* K, const float* inv_K,
+                   const float* T, const float* flow, long long flow_image_stride, long long flow_plane_stride, long long flow_row_stride,
+                   const unsigned char* valid, float* rigid, float* excess, unsigned char* label, int N, int H, int W, float alpha,
+                   float beta, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
