@@ -1,5 +1,6 @@
-"""What every Python wrapper in front of a kernel shares: the one argument check, the one shape refusal and the one alignment
-rule.  Depends on torch and _lib alone, so ops.py and the RAFT family (_raft_host) can both import it."""
+"""What every Python wrapper in front of a kernel shares: the one argument check, the one shape refusal, the one alignment
+rule and the one rule for reading a view in place.  Depends on torch and _lib alone, so ops.py and the RAFT family (_raft_host)
+can both import it."""
 import torch
 
 from ._lib import DvsError
@@ -26,6 +27,34 @@ def shaped(op, name, t, what, *shapes, like=None):
         raise DvsError("%s: %s must be %s = %s, got %s" % (op, name, what, " or ".join(str(s) for s in shapes), tuple(t.shape)))
     if like is not None and t.device != like.device:
         raise DvsError("%s: %s is on %s, not on %s" % (op, name, t.device, like.device))
+
+
+def not_negative(who, **values):
+    """The values as floats; refuses, naming all of them, unless every one is finite and not negative."""
+    got = tuple(float(v) for v in values.values())
+    if not all(0.0 <= v < float("inf") for v in got):
+        raise DvsError("%s: %s must be finite and not negative" % (who, ", ".join("%s=%r" % kv for kv in values.items())))
+    return got
+
+
+def dense_view(t, inner=1):
+    """(tensor, stride in elements of every dim in front of the innermost run, outermost first, ...) with which a kernel that takes
+    those strides reads `t`: `t` itself where the innermost run is dense and nothing overlaps, else ONE dense copy -- a layout a
+    kernel does not address is never read as if it were dense.  inner=1: the run is the last dim, with unit stride; inner=3: the
+    last two dims, a last dim of size 3 with stride 1 behind a dim of stride 3 (uint8 pixels).  Walking outwards from the run, a
+    dim of size 1 takes the extent of what lies inside it as its stride (whatever torch reports for it), and any other dim must
+    have a stride of at least that extent.  So a dense tensor, a batch or channel slice, a crop and a view at a storage offset are
+    read in place; a transposed, an expanded or an overlapping one is copied.  Stride arithmetic only: any device."""
+    n, shape, strides, extent = t.dim(), t.shape, list(t.stride()), 1
+    front = n - (1 if inner == 1 else 2)
+    for d in reversed(range(n)):
+        if shape[d] == 1:
+            strides[d] = extent
+        elif strides[d] < extent or (d >= front and strides[d] != extent):
+            t = t.contiguous()
+            return (t,) + tuple(t.stride()[:front])
+        extent += (shape[d] - 1) * strides[d]
+    return (t,) + tuple(strides[:front])
 
 
 def aligned(t, memory_format=torch.contiguous_format, bytes=16):

@@ -7,47 +7,22 @@ This module adds the two optional extras a real-time loop wants:
 
   * `depth_net.inference_scales = (0,)`   skip the three coarse disparity heads nobody reads at inference;
   * `Graphed(net, example)`               capture `net(example)` into a HIP graph and replay it per frame;
-  * `FramePredictor(depth, pose, ...)`    the whole per-frame work with PoseNet and DepthNet on two streams (and, by
-                                          default, as one graph with a fork / join): at batch 1 neither network fills
-                                          the chip, so running them side by side is worth more than the graph;
-  * `CloudPredictor(depth, pose, ...)`    FramePredictor + the output stage every inference caller of the reference does in
-                                          numpy: world pose chain and coloured point cloud on the device (pointcloud.py),
+  * `FramePredictor(depth, pose, ...)`    the whole per-frame work, PoseNet and DepthNet side by side on two streams (at batch 1
+                                          neither fills the chip), by default as one graph with a fork / join;
+  * `CloudPredictor(depth, pose, ...)`    FramePredictor + world pose chain and coloured point cloud on the device (pointcloud.py)
                                           inside the same graph, then one asynchronous copy into pinned host memory.
 """
 import torch
 
-from . import _lib, nn_ops
-
-
-def _fold_snapshot():
-    """(generation, references to every folded-BatchNorm tensor currently cached).  A captured graph holds raw pointers to
-    those tensors; nn_ops._fold_cache may replace an entry later (new weights, optimiser step) and the old tensors would
-    be freed under the graph -- the holder keeps them alive, the generation tells a replay that they are stale."""
-    return nn_ops.generation(), [(w, b) for (_, w, b) in nn_ops._fold_cache.values()]
-
-
-class _WeightsWatch:
-    """torch-visible modification state of every parameter / buffer of some networks (in-place torch updates,
-    load_state_dict bump `_version`).  One attribute read per tensor and replay: ~25 us for both networks."""
-
-    def __init__(self, *nets):
-        self.tensors = [t for net in nets for t in list(net.parameters()) + list(net.buffers())]
-        self.ptrs = tuple(t.data_ptr() for t in self.tensors)
-        self.seen = self.versions()
-
-    def versions(self):
-        return sum(t._version for t in self.tensors)
-
-    def changed(self):
-        return self.versions() != self.seen
+from . import _lib
+from ._graph import CapturedStep, HostRing
 
 
 class Graphed:
     """net(x) for one fixed input shape, replayed from a captured HIP graph.
 
     The returned tensors are the graph's static outputs: consume (or clone) them before the next call.  The BatchNorm fold is part
-    of the capture; the object keeps the folded tensors alive and re-captures by itself when the weights or buffers
-    change (torch version counters, nn_ops.generation() for the library's raw-pointer writers)."""
+    of the capture, which is made again by itself when the weights or buffers change (_graph.CapturedStep)."""
 
     def __init__(self, net, example, warmup=3):
         if net.training:
@@ -57,25 +32,21 @@ class Graphed:
         self.net = net
         self.static_in = example.detach().clone()
         self.warmup = warmup
+        self._captured = CapturedStep(self._step, (net,))
         self.refresh()
 
+    def _step(self):
+        return self.net(self.static_in)
+
+    graph = property(lambda self: self._captured.graph)
+    static_out = property(lambda self: self._captured.out)
+
     def refresh(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():        # warm-up off the capture: lazy initialisation, fold cache
-            for _ in range(self.warmup):
-                self.net(self.static_in)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.static_out = self.net(self.static_in)
-        self._gen, self._held = _fold_snapshot()
-        self._watch = _WeightsWatch(self.net)
+        self._captured.capture(self.warmup)
 
     def stale(self):
         """True when the weights or BatchNorm buffers changed since the capture (the fold is part of the graph)."""
-        return self._gen != nn_ops.generation() or self._watch.changed()
+        return self._captured.stale()
 
     def __call__(self, x):
         if x.shape != self.static_in.shape:
@@ -83,7 +54,7 @@ class Graphed:
         if self.stale():
             self.refresh()                   # re-fold and re-capture: never replay pointers to a replaced fold
         self.static_in.copy_(x, non_blocking=True)
-        self.graph.replay()
+        self._captured.replay()
         return self.static_out
 
 
@@ -102,27 +73,23 @@ class FramePredictor:
         self.depth_net, self.pose_net = depth_net, pose_net
         self.min_depth, self.max_depth, self.invert = min_depth, max_depth, invert
         self.side = torch.cuda.Stream(device=target.device)
-        self.graph = None
+        self._captured = None
         if graph:
             self.s_target, self.s_pair = target.detach().clone(), pair.detach().clone()
-            warm = torch.cuda.Stream(device=target.device)
-            warm.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(warm), torch.no_grad():
-                for _ in range(warmup):
-                    self._run(self.s_target, self.s_pair)
-            torch.cuda.current_stream().wait_stream(warm)
-            torch.cuda.synchronize()
-            self._capture()
+            self._captured = CapturedStep(self._step, (depth_net, pose_net), state=self._state)
+            self._captured.capture(warmup)
 
-    def _capture(self):
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.static_out = self._run(self.s_target, self.s_pair)
-        self._gen, self._held = _fold_snapshot()
-        self._watch = _WeightsWatch(self.depth_net, self.pose_net)
+    def _step(self):
+        return self._run(self.s_target, self.s_pair)
+
+    graph = property(lambda self: self._captured and self._captured.graph)
+    static_out = property(lambda self: self._captured.out)
+
+    def _state(self):                                           # the persistent tensors _run advances in place
+        return []
 
     def stale(self):
-        return self.graph is not None and (self._gen != nn_ops.generation() or self._watch.changed())
+        return self._captured is not None and self._captured.stale()
 
     def _run(self, target, pair):
         main = torch.cuda.current_stream()
@@ -136,18 +103,15 @@ class FramePredictor:
         return T, depth, disp
 
     def __call__(self, target, pair):
-        if self.graph is None:
+        if self._captured is None:
             with torch.no_grad():
                 return self._run(target, pair)
-        if self.stale():
-            with torch.no_grad():
-                self._run(self.s_target, self.s_pair)           # refold eagerly (fills the cache), then re-capture
-            torch.cuda.synchronize()
-            self._capture()
+        if self._captured.stale():
+            self._captured.capture(1)                           # one eager step refolds (fills the cache), then the re-capture
         self.s_target.copy_(target, non_blocking=True)
         self.s_pair.copy_(pair, non_blocking=True)
-        self.graph.replay()
-        return self.static_out
+        self._captured.replay()
+        return self._captured.out
 
 
 class Frame:
@@ -161,31 +125,22 @@ class Frame:
         self._slot, self._batch = slot, batch
 
     def wait(self):
-        self._slot["event"].synchronize()
+        self._slot.wait()
         return self
 
-    @property
-    def count(self):
-        """Records per image, numpy int32 [B]."""
-        return self.wait()._slot["count"].numpy()
+    def _host(name, doc):
+        return property(lambda self: self._slot.wait()[name].numpy(), doc=doc)
+
+    count = _host("count", "Records per image, numpy int32 [B].")
+    world_pose = _host("world", "World pose after this frame, numpy [4,4] (after the last image of the batch).")
+    tq = _host("tq", "(tx, ty, tz, qx, qy, qz, qw) of the world pose after each image, numpy [B,7].")
 
     @property
     def records(self):
         """pointcloud.as_records view: a RECORD_DTYPE array for batch 1, a list of them otherwise."""
         from . import pointcloud
-        self.wait()
-        r = pointcloud.as_records(self._slot["records"], self._slot["count"].numpy())
+        r = pointcloud.as_records(self._slot.wait()["records"], self.count)
         return r[0] if self._batch == 1 else r
-
-    @property
-    def world_pose(self):
-        """World pose after this frame, numpy [4,4] (after the last image of the batch)."""
-        return self.wait()._slot["world"].numpy()
-
-    @property
-    def tq(self):
-        """(tx, ty, tz, qx, qy, qz, qw) of the world pose after each image, numpy [B,7]."""
-        return self.wait()._slot["tq"].numpy()
 
 
 class CloudPredictor(FramePredictor):
@@ -199,10 +154,7 @@ class CloudPredictor(FramePredictor):
     (the ROS2 node's cloud; the pose chain still runs and `left` only shapes nothing then).  stride / z_range as
     pointcloud.depth_to_cloud (z_range switches compact mode on).  d2h (compact mode only): "full" copies the whole
     capacity and slices on the host after the event; "count" copies `count` first, waits for it inside the call, then copies
-    count[b] records per image.  init: start pose.
-
-    The graph mutates persistent state (`chain.world`): warm-up runs and the eager refold before a re-capture go to a scratch
-    world, so the pose advances exactly once per call."""
+    count[b] records per image.  init: start pose.  A capture puts `chain.world` back: the pose advances exactly once per call."""
 
     def __init__(self, depth_net, pose_net, target, pair, K, *, frame="world", left=None, init=None, stride=1, z_range=None,
                  min_depth=0.1, max_depth=10.0, invert=False, graph=True, d2h="full", warmup=3):
@@ -219,8 +171,6 @@ class CloudPredictor(FramePredictor):
         self.frame, self.stride, self.z_range, self.d2h = frame, stride, z_range, d2h
         self.K = K.detach().float().contiguous().clone()
         self.chain = pointcloud.PoseChain(dev, left=left, init=init)
-        self._scratch = self.chain.world.clone()
-        self._world = self._scratch                             # where _run advances the pose: scratch until the capture
         cfg = pointcloud.make_cfg(B, H, W, stride, (min_depth, max_depth), z_range, self.K.shape[1])
         n_max = pointcloud.capacity(cfg)
         f32 = dict(device=dev, dtype=torch.float32)
@@ -229,13 +179,9 @@ class CloudPredictor(FramePredictor):
         self.d_count = torch.zeros(B, device=dev, dtype=torch.int32)
         ws = pointcloud.workspace_bytes(cfg)
         self.d_ws = torch.empty(ws, device=dev, dtype=torch.uint8) if ws else None
-        pin = lambda *s, **k: torch.zeros(*s, pin_memory=True, **k)
-        self._slots = [dict(records=pin(B, n_max, 4), count=pin(B, dtype=torch.int32), tq=pin(B, 7), world=pin(4, 4),
-                            event=torch.cuda.Event()) for _ in range(2)]
-        self._n = 0
+        self._ring = HostRing()
         super().__init__(depth_net, pose_net, target, pair, min_depth=min_depth, max_depth=max_depth, invert=invert,
                          graph=graph, warmup=warmup)
-        self._world = self.chain.world                          # eager mode; graph mode switched in _capture already
 
     @property
     def world(self):
@@ -245,9 +191,8 @@ class CloudPredictor(FramePredictor):
     def reset(self, init=None):
         self.chain.reset(init)
 
-    def _capture(self):
-        self._world = self.chain.world                          # capturing records the launch, it does not run it
-        super()._capture()
+    def _state(self):
+        return [self.chain.world]
 
     def _run(self, target, pair):
         main = torch.cuda.current_stream()
@@ -255,7 +200,7 @@ class CloudPredictor(FramePredictor):
         with torch.cuda.stream(self.side):
             aa, t = self.pose_net(pair)
             T = self._t(aa[:, 0], t[:, 0], invert=self.invert)
-            self.chain.step(T, self.d_poses, self.d_M, self.d_tq, world=self._world)
+            self.chain.step(T, self.d_poses, self.d_M, self.d_tq)
         disp = self.depth_net(target)[("disp", 0)]
         _, depth = self._d2d(disp, self.min_depth, self.max_depth)
         main.wait_stream(self.side)
@@ -265,22 +210,8 @@ class CloudPredictor(FramePredictor):
         return T, depth, disp
 
     def __call__(self, target, pair):
-        if self.graph is None:
-            with torch.no_grad():
-                out = self._run(target, pair)
-        else:
-            if self.stale():
-                self._world = self._scratch                     # refold eagerly without touching the pose, then re-capture
-                with torch.no_grad():
-                    self._run(self.s_target, self.s_pair)
-                torch.cuda.synchronize()
-                self._capture()
-            self.s_target.copy_(target, non_blocking=True)
-            self.s_pair.copy_(pair, non_blocking=True)
-            self.graph.replay()
-            out = self.static_out
-        slot = self._slots[self._n & 1]
-        self._n += 1
+        out = super().__call__(target, pair)
+        slot = self._ring.next(records=self.d_records, count=self.d_count, tq=self.d_tq, world=self.chain.world)
         slot["count"].copy_(self.d_count, non_blocking=True)
         if self.z_range is not None and self.d2h == "count":
             slot["event"].record()

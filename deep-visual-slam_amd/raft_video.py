@@ -22,18 +22,20 @@
     for frame in frames:                               # uint8 [H,W,3] or [N,H,W,3], on the GPU or on the host
         r = stream.push(frame)                         # None for the first frame, then r.flow_up, r.flow_low, r.image (until the next push)
 
-forward_interpolate and flow_to_image are csrc/flowstage.hip (include/dvslam.h states their arithmetic); nothing here copies to
-the host or synchronises (FlowStream's host=True copies are asynchronous; reading one waits for its event).  FlowPredictor's
-padding is F.pad and a slice: not hot, it stays ATen.  GPU only; fp32 flows, uint8 frames and pictures.
+forward_interpolate and flow_to_image are csrc/flowstage.hip (include/dvslam.h states their arithmetic); nothing here synchronises
+(host=True copies are asynchronous).  FlowPredictor's padding stays ATen: not hot.  GPU only; fp32 flows, uint8 frames and pictures.
 """
+import copy
+from functools import partial
 from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._graph import CapturedStep, HostRing
+from ._host import dense_view, gpu_arg, not_negative
 from ._lib import DvsError, check
-from ._raft_host import gpu_arg
 from .raft import RAFT, SmallRAFT
 
 MAX_POINTS = 65536          # dvs_forward_interp is a brute-force search: h * w sources per image at the most
@@ -63,16 +65,17 @@ def forward_interpolate(flow):
     return out if batched else out[0]
 
 
+_rows = _planes = dense_view                # a flow [N,2,H,W]: image, plane and row stride; a depth [N,H,W]: image and row stride
+_packed = partial(dense_view, inner=3)          # uint8 frames [N,H,W,3]: image and row stride in bytes
+
+
 def _strided(f):
-    """(tensor, plane stride, row stride) with which dvs_flow_to_image reads `f` [N,2,H,W]: `f` itself if it has unit stride along
-    W, rows and planes that do not overlap and images two planes apart (every slice of a contiguous flow has), else a copy."""
-    N, _, H, W = f.shape
-    s0, s1, s2, s3 = f.stride()
-    row = s2 if H > 1 else W
-    if ((s3 == 1 or W == 1) and row >= W and s1 >= (H - 1) * row + W and (N == 1 or s0 == 2 * s1) and f.data_ptr() % 4 == 0):
-        return f, s1, row
-    f = f.contiguous()
-    return f, H * W, W
+    """(tensor, plane stride, row stride) with which dvs_flow_to_image reads `f` [N,2,H,W]: the entry takes no image stride, so
+    a batch whose images do not lie two planes apart is copied as well."""
+    kept, image, plane, row = _rows(f)
+    if f.shape[0] > 1 and image != 2 * plane:
+        kept, image, plane, row = _rows(f.contiguous())
+    return kept, plane, row
 
 
 def flow_to_image(flow, clip_flow=None, convert_to_bgr=False):
@@ -95,20 +98,6 @@ def flow_to_image(flow, clip_flow=None, convert_to_bgr=False):
     return out if batched else out[0]
 
 
-def _rows(f):
-    """(tensor, image stride, plane stride, row stride) in elements with which dvs_flow_consistency reads `f` [N,2,H,W]: `f` itself
-    where its rows are dense and rows, planes and images do not overlap (a contiguous flow, a batch or channel slice, the
-    un-padded view of a padded flow, a flow at a storage offset), else ONE dense copy."""
-    N, _, H, W = f.shape
-    s0, s1, s2, s3 = f.stride()
-    row = s2 if H > 1 else W
-    extent = (H - 1) * row + W
-    image = s0 if N > 1 else s1 + extent
-    if (s3 == 1 or W == 1) and row >= W and s1 >= extent and image >= s1 + extent:
-        return f, image, s1, row
-    return f.contiguous(), 2 * H * W, H * W, W
-
-
 def flow_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5, excess=False):
     """The forward-backward check of UnFlow (Meister et al. 2018, eq. 2) on the device, both directions in ONE launch
     (dvs_flow_consistency; include/dvslam.h states the arithmetic).  flow_fw [2,H,W] or [N,2,H,W] fp32 on image 1's grid (image 1 ->
@@ -125,9 +114,7 @@ def flow_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5, excess=False):
     bw, _ = _flow_arg(who + ": flow_bw", flow_bw, "[2,H,W] or [N,2,H,W]")
     if fw.shape != bw.shape or fw.device != bw.device:
         raise DvsError("%s: flow_fw %s on %s, flow_bw %s on %s" % (who, tuple(fw.shape), fw.device, tuple(bw.shape), bw.device))
-    alpha, beta = float(alpha), float(beta)
-    if not (0.0 <= alpha < float("inf") and 0.0 <= beta < float("inf")):
-        raise DvsError("%s: alpha=%r, beta=%r must be finite and not negative" % (who, alpha, beta))
+    alpha, beta = not_negative(who, alpha=alpha, beta=beta)
     fw, fw_image, fw_plane, fw_row = _rows(fw)
     bw, bw_image, bw_plane, bw_row = _rows(bw)
     N, _, H, W = fw.shape
@@ -139,19 +126,6 @@ def flow_consistency(flow_fw, flow_bw, alpha=0.01, beta=0.5, excess=False):
           "dvs_flow_consistency")
     out = (valid[0], valid[1]) + ((over[0], over[1]) if excess else ())
     return out if batched else tuple(t[0] for t in out)
-
-
-def _planes(d):
-    """(tensor, image stride, row stride) in elements with which dvs_rigid_flow reads the depth `d` [N,H,W]: `d` itself where its
-    rows are dense and rows and images do not overlap (the policy of _rows), else ONE dense copy."""
-    N, H, W = d.shape
-    s0, s1, s2 = d.stride()
-    row = s1 if H > 1 else W
-    extent = (H - 1) * row + W
-    image = s0 if N > 1 else extent
-    if (s2 == 1 or W == 1) and row >= W and image >= extent:
-        return d, image, row
-    return d.contiguous(), H * W, W
 
 
 def _matrix_arg(who, m, N, single):
@@ -202,10 +176,7 @@ def rigid_flow(depth, T, K, inv_K=None, flow=None, valid=None, alpha=0.01, beta=
     their strides; any other layout is copied once."""
     who = "rigid_flow"
     N, H, W = _rigid_args(who, depth, T, K, inv_K, flow, valid)
-    alpha, beta, eps = float(alpha), float(beta), float(eps)
-    inf = float("inf")
-    if not (0.0 <= alpha < inf and 0.0 <= beta < inf and 0.0 <= eps < inf):
-        raise DvsError("%s: alpha=%r, beta=%r, eps=%r must be finite and not negative" % (who, alpha, beta, eps))
+    alpha, beta, eps = not_negative(who, alpha=alpha, beta=beta, eps=eps)
     if excess and flow is None:
         raise DvsError("%s: excess=True needs a flow" % who)
     d, d_image, d_row = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
@@ -249,6 +220,15 @@ class InputPadder:
         return x[..., top:ht - bottom, left:wd - right]
 
 
+def _low_up(model, call, a, b, iters, flow_init):
+    """(flow_low, flow_up at the padded size) of call(a, b), call being `model`, model.refine or model.refine_pair: RAFT has a test
+    mode; SmallRAFT's counterpart is last_only and its flow_low."""
+    if isinstance(model, RAFT):
+        return call(a, b, iters=iters, flow_init=flow_init, test_mode=True)
+    up = call(a, b, iters=iters, flow_init=flow_init, last_only=True)[-1]
+    return model.flow_low[-1], up
+
+
 class FlowPredictor:
     """One call per frame pair around SmallRAFT or RAFT in eval mode: replicate-pad, run the model under no_grad in test mode,
     keep forward_interpolate(flow_low) as the next call's flow_init (warm_start), un-pad, colour (image).
@@ -268,13 +248,6 @@ class FlowPredictor:
     def reset(self):
         self.flow_init, self._shape = None, None
 
-    def _run(self, image1, image2):
-        """(flow_low, flow_up) of the padded pair: RAFT has a test mode; SmallRAFT's counterpart is last_only and its flow_low."""
-        if isinstance(self.model, RAFT):
-            return self.model(image1, image2, iters=self.iters, flow_init=self.flow_init, test_mode=True)
-        up = self.model(image1, image2, iters=self.iters, flow_init=self.flow_init, last_only=True)[-1]
-        return self.model.flow_low[-1], up
-
     @torch.no_grad()
     def pred(self, image1, image2):
         if self.model.training:
@@ -291,7 +264,8 @@ class FlowPredictor:
                            % (self._shape + shape))
         padder = InputPadder(image1.shape, self.pad_mode)
         a, b = padder.pad(image1, image2)
-        flow_low, flow_pad = self._run(a, b)                # a padded size the model refuses: the model's own error
+        # a padded size the model refuses: the model's own error
+        flow_low, flow_pad = _low_up(self.model, self.model, a, b, self.iters, self.flow_init)
         self._shape = shape
         if self.warm_start:
             self.flow_init = forward_interpolate(flow_low)
@@ -312,20 +286,6 @@ def _frames_u8(who, frame):
     if frame.dim() not in (3, 4) or frame.shape[-1] != 3 or min(frame.shape) < 1:
         raise DvsError("%s: [H,W,3] or [N,H,W,3] expected, got %s" % (who, tuple(frame.shape)))
     return frame if frame.dim() == 4 else frame[None]
-
-
-def _packed(f):
-    """(tensor, image stride, row stride) in bytes with which dvs_frame_ingest reads `f` [N,H,W,3]: `f` itself where its pixels are
-    three adjacent bytes, its rows do not overlap and its images neither (a dense frame, a batch slice, a crop of a larger frame,
-    a frame at any storage offset), else ONE dense copy (a planar [3,H,W] frame seen through permute, a transposed or an expanded
-    one): a layout the kernel does not address is never read as if it were dense."""
-    N, H, W, _ = f.shape
-    s0, s1, s2, s3 = f.stride()
-    row = s1 if H > 1 else 3 * W
-    image = s0 if N > 1 else (H - 1) * row + 3 * W
-    if s3 == 1 and (s2 == 3 or W == 1) and row >= 3 * W and image >= (H - 1) * row + 3 * W:
-        return f, image, row
-    return f.contiguous(), 3 * H * W, 3 * W
 
 
 def frame_ingest(frame, pad=(0, 0, 0, 0), bgr=False):
@@ -370,27 +330,17 @@ class FlowFrame:
     def wait(self):
         if self._slot is None:
             raise DvsError("FlowStream: host copies are made with host=True only")
-        self._slot["event"].synchronize()
+        self._slot.wait()
         return self
 
-    @property
-    def flow_low_host(self):
-        return self.wait()._slot["flow_low"].numpy()
+    def _host(self, name):
+        t = self.wait()._slot[name]
+        return t.numpy() if t is not None else None
 
-    @property
-    def image_host(self):
-        image = self.wait()._slot["image"]
-        return image.numpy() if image is not None else None
-
-    @property
-    def valid_host(self):
-        valid = self.wait()._slot["valid"]
-        return valid.numpy() if valid is not None else None
-
-    @property
-    def motion_host(self):
-        motion = self.wait()._slot.get("motion")
-        return motion.numpy() if motion is not None else None
+    flow_low_host = property(lambda self: self._host("flow_low"))
+    image_host = property(lambda self: self._host("image"))
+    valid_host = property(lambda self: self._host("valid"))
+    motion_host = property(lambda self: self._host("motion"))
 
 
 class FlowStream:
@@ -412,19 +362,15 @@ class FlowStream:
     uint8 resize first and pushes its output.
 
     graph=True (the default: measured faster than the eager stream for both models; graph=False issues the
-    same launches eagerly and returns fresh tensors): everything after the copy of the frame into a static uint8 buffer -- ingest, both encoders, the correlation
-    block, all `iters` update steps, the upsampling, forward_interpolate into the persistent flow_init buffer, the colouring and
-    the hand-over of this frame's features to the "previous" slot -- is one HIP graph, captured on one stream at the first push
-    of a shape.  The returned tensors are then the graph's static outputs: consume (or clone) them before the next push.  A zeroed
-    flow_init is the cold start, so reset() zeroes the buffer and marks the slot empty without a new capture; the graph is
-    captured again by itself when the weights or the BatchNorm buffers changed (stale()).
+    same launches eagerly and returns fresh tensors): everything after the copy of the frame into a static uint8 buffer, the kept
+    flow and the hand-over of this frame's features included, is one HIP graph, captured on one stream at the first push of a shape
+    and again when stale().  The returned tensors are then the graph's static outputs: consume (or clone) them before the
+    next push.  A zeroed flow_init is the cold start, so reset() zeroes the buffer and marks the slot empty without a new capture.
     host=True: the picture and flow_low are also copied asynchronously into two alternating pinned host buffers (FlowFrame).
     bidirectional=True: each pair is model.refine_pair(previous, current), ONE loop at batch 2N (rows 0 .. N-1 previous -> current,
     rows N .. 2N-1 current -> previous; no further encoder pass), the kept flow is forward_interpolate of all 2N flow_low, and
     flow_consistency(flow_up, flow_up_bw, fb_alpha, fb_beta) on the un-padded views adds the two validity masks, inside the same
-    graph.  The default changes nothing.  Measured: DESIGN.md section 23.
-    The rigid mode (rigid flow from depth and pose, and a moving-object label per pixel) is RigidFlowStream, below: this
-    constructor's signature stays as it is."""
+    graph.  The default changes nothing.  Measured: DESIGN.md section 23.  The rigid mode is RigidFlowStream, below."""
 
     def __init__(self, model, iters=12, warm_start=True, pad_mode="sintel", image=True, convert_to_bgr=False, bgr=False,
                  graph=True, host=False, warmup=2, bidirectional=False, fb_alpha=0.01, fb_beta=0.5):
@@ -435,17 +381,18 @@ class FlowStream:
         self.model, self.iters, self.warm_start, self.pad_mode = model, int(iters), bool(warm_start), pad_mode
         self.image, self.convert_to_bgr, self.bgr = bool(image), bool(convert_to_bgr), bool(bgr)
         self.use_graph, self.host, self.warmup = bool(graph), bool(host), int(warmup)
-        self.bidirectional, self.fb_alpha, self.fb_beta = bool(bidirectional), float(fb_alpha), float(fb_beta)
-        if not (0.0 <= self.fb_alpha < float("inf") and 0.0 <= self.fb_beta < float("inf")):
-            raise DvsError("FlowStream: fb_alpha=%r, fb_beta=%r must be finite and not negative" % (fb_alpha, fb_beta))
+        self.bidirectional = bool(bidirectional)
+        self.fb_alpha, self.fb_beta = not_negative("FlowStream", fb_alpha=fb_alpha, fb_beta=fb_beta)
         self.flow_init = None               # eager: the kept flow or None; graph: the persistent buffer
         self._prev, self._shape = None, None  # the previous frame's features (graph: the slot, with _have_prev)
         self._have_prev = False
-        self.graph, self._graph_shape = None, None
-        self._slots, self._n = None, 0
+        self._captured, self._graph_shape = None, None
+        self._ring = HostRing()
         self.frame_copied = None            # the event behind the last host frame's H2D copy
         self.rigid, self.rigid_alpha, self.rigid_beta = False, 0.01, 0.5      # RigidFlowStream's mode
         self._geo = None                    # graph mode: the static depth, T, K and inv_K the rigid-flow node reads
+
+    graph = property(lambda self: self._captured and self._captured.graph)
 
     def reset(self):
         """A new sequence: the next push encodes its frame and returns None."""
@@ -456,92 +403,67 @@ class FlowStream:
             self.flow_init.zero_()
 
     # ---- one step, eager or under capture --------------------------------------------------------------------------------------
-    def _refine(self, prev, feat, flow_init):
-        """(flow_low, flow_up at the padded size): RAFT has a test mode; SmallRAFT's counterpart is last_only and its flow_low."""
-        refine = self.model.refine_pair if self.bidirectional else self.model.refine     # refine_pair: batch 2N, forward rows first
-        if isinstance(self.model, RAFT):
-            return refine(prev, feat, iters=self.iters, flow_init=flow_init, test_mode=True)
-        up = refine(prev, feat, iters=self.iters, flow_init=flow_init, last_only=True)[-1]
-        return self.model.flow_low[-1], up
-
     def _encode(self, frames, padder):
         return self.model.encode_frame(frame_ingest(frames, padder._pad, self.bgr))
 
     def _pair(self, prev, feat, flow_init, padder, geo=None):
-        """(FlowFrame's fields in the order of its arguments, without the slot; the next flow_init).  geo: a rigid stream's
-        (depth, T, K, inv_K)."""
-        flow_low, flow_pad = self._refine(prev, feat, flow_init)
+        """(the pair's FlowFrame, without a slot; the next flow_init).  geo: a rigid stream's (depth, T, K, inv_K)."""
+        refine = self.model.refine_pair if self.bidirectional else self.model.refine     # refine_pair: batch 2N, forward rows first
+        flow_low, flow_pad = _low_up(self.model, refine, prev, feat, self.iters, flow_init)
         kept = forward_interpolate(flow_low) if self.warm_start else None
         flow_up = padder.unpad(flow_pad)
-        both = ()
+        frame = FlowFrame(flow_low, flow_up, None)
         if self.bidirectional:                              # the mask is taken on the un-padded views: the padding is not the image
             N = flow_up.shape[0] // 2
-            both = (flow_low[N:], flow_up[N:]) + flow_consistency(flow_up[:N], flow_up[N:], self.fb_alpha, self.fb_beta)
-            flow_low, flow_up = flow_low[:N], flow_up[:N]
-        image = flow_to_image(flow_up, convert_to_bgr=self.convert_to_bgr) if self.image else None
+            frame.flow_low, frame.flow_up = flow_low[:N], flow_up[:N]
+            frame.flow_low_bw, frame.flow_up_bw = flow_low[N:], flow_up[N:]
+            frame.valid, frame.valid_bw = flow_consistency(frame.flow_up, frame.flow_up_bw, self.fb_alpha, self.fb_beta)
+        if self.image:
+            frame.image = flow_to_image(frame.flow_up, convert_to_bgr=self.convert_to_bgr)
         if self.rigid:                                      # on the same un-padded view, masked by the forward validity
-            both = (both or (None,) * 4) + rigid_flow(*geo, flow=flow_up, valid=both[2] if both else None, alpha=self.rigid_alpha,
-                                                      beta=self.rigid_beta)
-        return (flow_low, flow_up, image) + both, kept
+            frame.rigid, frame.motion = rigid_flow(*geo, flow=frame.flow_up, valid=frame.valid, alpha=self.rigid_alpha,
+                                                   beta=self.rigid_beta)
+        return frame, kept
 
-    def _graph_step(self, padder):
-        """What the graph holds: s_frame -> outputs, flow_init and the previous slot advanced in place."""
-        feat = self._encode(self.s_frame, padder)
-        out, kept = self._pair(self._prev, feat, self.flow_init, padder, self._geo)
+    def _graph_step(self):
+        """What the graph holds: s_frame -> a FlowFrame, flow_init and the previous slot advanced in place."""
+        feat = self._encode(self.s_frame, self._padder)
+        frame, kept = self._pair(self._prev, feat, self.flow_init, self._padder, self._geo)
         if kept is not None:
             self.flow_init.copy_(kept)
         for name in ("fmap", "net", "inp"):                 # copy_ bumps inp's version: the update block's hoisted terms are re-made
             getattr(self._prev, name).copy_(getattr(feat, name))
-        return out
+        return frame
 
     # ---- capture -----------------------------------------------------------------------------------------------------------------
     def _derived(self):
         return [m._weights for m in (self.model.fnet, self.model.cnet, self.model.update_block)]
 
-    def _capture(self, frames, padder):
-        """Warm-up on a side stream, then the capture.  Both advance nothing: the kept flow and the previous slot are put back."""
-        from . import inference
-        first = self._graph_shape != self._shape_of(frames)
-        if first:
-            self.graph = None
-            self.s_frame = torch.empty(tuple(frames.shape), device=frames.device, dtype=torch.uint8)
-            self.s_frame.copy_(frames)
-            with torch.no_grad():
-                feat = self._encode(self.s_frame, padder)   # a padded size the model refuses: the model's own error
-            self._prev = SimpleNamespace(fmap=feat.fmap.clone(), net=feat.net.clone(), inp=feat.inp.clone())
-            N, _, h, w = feat.fmap.shape
-            pairs = 2 * N if self.bidirectional else N      # bidirectional: the kept flow of both directions, forward rows first
-            self.flow_init = torch.zeros((pairs, 2, h, w), device=frames.device) if self.warm_start else None
-            if self.rigid:                                  # filled before every replay, as s_frame is
-                f32 = dict(device=frames.device, dtype=torch.float32)
-                self._geo = (torch.ones((N,) + tuple(frames.shape[1:3]), **f32),) + tuple(
-                    torch.eye(4, **f32).repeat(N, 1, 1) for _ in range(3))
-        state = [t.clone() for t in self._state()]
-        side = torch.cuda.Stream(device=frames.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(self.warmup):
-                self._graph_step(padder)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.static_out = self._graph_step(padder)
-        self._gen, self._held = inference._fold_snapshot()
-        self._watch = inference._WeightsWatch(self.model)
-        self._held_derived = self._derived()                # the graph points into these operands: kept alive, compared in stale()
-        self._graph_shape = self._shape_of(frames)
-        for t, saved in zip(self._state(), state):
-            t.copy_(saved)
-
     def _state(self):
         return [self._prev.fmap, self._prev.net, self._prev.inp] + ([self.flow_init] if self.warm_start else [])
 
+    def _allocate(self, frames, padder):
+        """The first push of a shape: the static frame, the previous slot, the kept flow, a rigid stream's operands, a new graph."""
+        self._captured = self._graph_shape = None
+        self._padder = padder
+        self.s_frame = torch.empty(tuple(frames.shape), device=frames.device, dtype=torch.uint8)
+        self.s_frame.copy_(frames)
+        feat = self._encode(self.s_frame, padder)           # a padded size the model refuses: the model's own error
+        self._prev = SimpleNamespace(fmap=feat.fmap.clone(), net=feat.net.clone(), inp=feat.inp.clone())
+        N, _, h, w = feat.fmap.shape
+        pairs = 2 * N if self.bidirectional else N          # bidirectional: the kept flow of both directions, forward rows first
+        self.flow_init = torch.zeros((pairs, 2, h, w), device=frames.device) if self.warm_start else None
+        if self.rigid:                                      # filled before every replay, as s_frame is
+            f32 = dict(device=frames.device, dtype=torch.float32)
+            self._geo = (torch.ones((N,) + tuple(frames.shape[1:3]), **f32),) + tuple(
+                torch.eye(4, **f32).repeat(N, 1, 1) for _ in range(3))
+        self._captured = CapturedStep(self._graph_step, (self.model,), state=self._state, derived=self._derived)
+        self._captured.capture(self.warmup)
+        self._graph_shape = self._shape_of(frames)
+
     def stale(self):
         """True when the weights or BatchNorm buffers changed since the capture, or the operands derived from them were re-made."""
-        from . import nn_ops
-        return self.graph is not None and (self._gen != nn_ops.generation() or self._watch.changed()
-                                           or any(a is not b for a, b in zip(self._derived(), self._held_derived)))
+        return self._captured is not None and self._captured.stale()
 
     @staticmethod
     def _shape_of(frames):
@@ -575,10 +497,11 @@ class FlowStream:
         self._shape = shape
         if out is None:
             return None
-        slot = None
+        if self.use_graph:                                  # `out` is the graph's own frame: every push hands out a fresh one
+            out = copy.copy(out)
         if self.host:
-            slot = self._host_slot(out)
-        return FlowFrame(out[0], out[1], out[2], slot, *out[3:])
+            out._slot = self._ring.put(flow_low=out.flow_low, image=out.image, valid=out.valid, motion=out.motion)
+        return out
 
     def _geo_args(self, frames, depth, T, K, inv_K):
         """A rigid stream's (depth, T, K, inv_K) for the pair this push completes, checked; None for the first frame of a
@@ -609,42 +532,22 @@ class FlowStream:
         return out
 
     def _push_graph(self, frames, padder, geo=None):
-        if self.graph is None or self._graph_shape != self._shape_of(frames):
+        if self._graph_shape != self._shape_of(frames):
             self._have_prev = False
-            self._capture(frames, padder)
-        elif self.stale():
-            self._capture(frames, padder)
+            self._allocate(frames, padder)
+        elif self._captured.stale():
+            self._captured.capture(self.warmup)
         self.s_frame.copy_(frames, non_blocking=True)
         if geo is not None:
             for static, t in zip(self._geo, geo):           # a [4,4] K or inv_K is broadcast over the images
                 static.copy_(t, non_blocking=True)
-        self.graph.replay()
+        self._captured.replay()
         if self._have_prev:
-            return self.static_out
+            return self._captured.out
         self._have_prev = True                              # the first frame of a sequence: only its features count
         if self.warm_start:
             self.flow_init.zero_()
         return None
-
-    def _host_slot(self, out):
-        valid = out[5] if self.bidirectional else None
-        motion = out[8] if self.rigid else None
-        if self._slots is None or self._slots[0]["flow_low"].shape != out[0].shape or (
-                out[2] is not None and self._slots[0]["image"].shape != out[2].shape):
-            pin = lambda t: torch.zeros(tuple(t.shape), dtype=t.dtype, pin_memory=True) if t is not None else None
-            self._slots = [dict(flow_low=pin(out[0]), image=pin(out[2]), valid=pin(valid), motion=pin(motion), event=torch.cuda.Event())
-                           for _ in range(2)]
-        slot = self._slots[self._n & 1]
-        self._n += 1
-        slot["flow_low"].copy_(out[0], non_blocking=True)
-        if out[2] is not None:
-            slot["image"].copy_(out[2], non_blocking=True)
-        if valid is not None:
-            slot["valid"].copy_(valid, non_blocking=True)
-        if motion is not None:
-            slot["motion"].copy_(motion, non_blocking=True)
-        slot["event"].record()
-        return slot
 
 
 class RigidFlowStream(FlowStream):
@@ -665,6 +568,5 @@ class RigidFlowStream(FlowStream):
 
     def __init__(self, model, *args, rigid=True, rigid_alpha=0.01, rigid_beta=0.5, **kw):
         super().__init__(model, *args, **kw)
-        self.rigid, self.rigid_alpha, self.rigid_beta = bool(rigid), float(rigid_alpha), float(rigid_beta)
-        if not (0.0 <= self.rigid_alpha < float("inf") and 0.0 <= self.rigid_beta < float("inf")):
-            raise DvsError("FlowStream: rigid_alpha=%r, rigid_beta=%r must be finite and not negative" % (rigid_alpha, rigid_beta))
+        self.rigid = bool(rigid)
+        self.rigid_alpha, self.rigid_beta = not_negative("FlowStream", rigid_alpha=rigid_alpha, rigid_beta=rigid_beta)
