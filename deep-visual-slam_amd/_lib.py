@@ -198,6 +198,9 @@ _SIGNATURES = {
     "dvs_flow_consistency": (C.c_int, ([_vp] + [C.c_longlong] * 3) * 2 + [_vp] * 4 + [C.c_int] * 3 + [C.c_float, C.c_float, _vp]),
     "dvs_rigid_flow": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp] + [C.c_longlong] * 3 + [_vp] * 4 + [C.c_int] * 3
                        + [C.c_float] * 3 + [_vp]),
+    "dvs_pose_fit_workspace": (C.c_size_t, [C.c_int] * 3),
+    "dvs_pose_fit": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp] + [C.c_longlong] * 3 + [_vp] * 5 + [C.c_size_t]
+                     + [C.c_int] * 4 + [C.c_float] * 3 + [_vp]),
 }
 
 _lib = None

@@ -12,6 +12,9 @@
     rigid_flow(depth, T, K, ...)   csrc/rigidflow.hip: the flow a static scene shows under a depth map and a camera motion, and a
                                    static / moving label for a measured flow against it, by one launch
     RigidFlowStream(model, ...)    FlowStream whose push also takes depth, T, K, inv_K and adds rigid and motion to every pair
+    fit_pose(depth, flow, K, ...)  csrc/posefit.hip: the camera motion that explains a measured flow under a depth map, by Gauss-Newton
+                                   on SE(3) with Huber weights, two launches a step
+    PoseFlowStream(model, ...)     RigidFlowStream that fits T to its own flow (two rounds: all pixels, then the static ones)
 
     pred = FlowPredictor(raft.RAFT({"small": False}).cuda().eval(), iters=12)
     for frame1, frame2 in pairs:                       # [B,3,H,W] fp32 in 0 .. 1 on the GPU, any H, W the padded model accepts
@@ -134,13 +137,14 @@ def _matrix_arg(who, m, N, single):
     gpu_arg(who, m, want, rank=(2, 3) if single else 3, ok=lambda shape: tuple(shape) in ((N, 4, 4),) + (((4, 4),) if single else ()))
 
 
-def _rigid_args(who, depth, T, K, inv_K, flow=None, valid=None, shape=None):
+def _rigid_args(who, depth, T, K, inv_K, flow=None, valid=None, shape=None, T_name="T"):
     """The argument checks of rigid_flow, made on the tensors' descriptions alone (before any launch or copy); `shape`: the
-    (N, H, W) the caller demands.  Returns (N, H, W)."""
+    (N, H, W) the caller demands; T_name: what the caller calls T (None: it has none to check).  Returns (N, H, W)."""
     gpu_arg(who + ": depth", depth, "[N,1,H,W] or [N,H,W] expected", rank=(3, 4),
             ok=lambda s: min(s) >= 1 and (len(s) == 3 or s[1] == 1) and (shape is None or (s[0], s[-2], s[-1]) == tuple(shape)))
     N, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
-    _matrix_arg(who + ": T", T, N, False)
+    if T_name is not None:
+        _matrix_arg(who + ": " + T_name, T, N, False)
     _matrix_arg(who + ": K", K, N, True)
     if inv_K is not None:
         _matrix_arg(who + ": inv_K", inv_K, N, True)
@@ -152,7 +156,7 @@ def _rigid_args(who, depth, T, K, inv_K, flow=None, valid=None, shape=None):
         if valid.dtype != torch.uint8 or tuple(valid.shape) != (N, H, W):
             raise DvsError("%s: valid: uint8 [%d,%d,%d] expected (the mask of flow_consistency), got %s %s"
                            % (who, N, H, W, valid.dtype, tuple(valid.shape)))
-    for name, t in (("T", T), ("K", K), ("inv_K", inv_K), ("flow", flow), ("valid", valid)):
+    for name, t in ((T_name, T), ("K", K), ("inv_K", inv_K), ("flow", flow), ("valid", valid)):
         if t is not None and t.device != depth.device:
             raise DvsError("%s: %s is on %s, depth on %s" % (who, name, t.device, depth.device))
     return N, H, W
@@ -195,6 +199,64 @@ def rigid_flow(depth, T, K, inv_K=None, flow=None, valid=None, alpha=0.01, beta=
     if f is None:
         return rigid
     return (rigid, label, over) if excess else (rigid, label)
+
+
+POSE_SUMS = 30              # dvs_pose_fit's sums per image: 21 of J^T J, 6 of J^T e, the cost, the weights, the judged count
+
+
+def pose_fit_workspace(N, H, W, device):
+    """The workspace of one fit_pose call at this shape: a uint8 tensor of dvs_pose_fit_workspace bytes."""
+    return torch.empty((int(_lib.lib().dvs_pose_fit_workspace(N, H, W)),), device=device, dtype=torch.uint8)
+
+
+def fit_pose(depth, flow, K, inv_K=None, T0=None, valid=None, iters=4, huber=1.0, damping=1e-6, eps=1e-7, normal=False,
+             workspace=None):
+    """The camera motion under which a STATIC scene of this depth shows this flow, on the device (dvs_pose_fit; include/dvslam.h
+    states the arithmetic): `iters` Gauss-Newton steps on SE(3) over the reprojection error of every judged pixel, with Huber
+    weights (huber=inf: plain least squares), two launches a step.  The inverse of rigid_flow, whose conventions it shares.
+
+    depth [N,1,H,W] or [N,H,W] fp32, of the flow's SOURCE frame; flow [N,2,H,W] fp32; K and inv_K [4,4] or [N,4,4] (inv_K=None
+    inverts K once with torch.linalg.inv on the device); T0 [N,4,4], the initial guess (None: the identity); valid uint8 [N,H,W]
+    or None: the pixels that take part (flow_consistency's mask, or rigid_flow's label == 1).  Returns (T, status): T fp32 [N,4,4]
+    maps points of the source camera into the target camera, status int32 [N] is 0 where every step was taken and 1 where one
+    was skipped (fewer than 6 judged pixels, a singular or non-finite system: T then stays where it was).  normal=True:
+    (T, status, normal), normal fp64 [N,30] = the sums at the final T (0 .. 20 the upper triangle of J^T W J, 21 .. 26 J^T W e, 27
+    the cost, 28 the sum of the weights, 29 the judged count).  workspace: a tensor of pose_fit_workspace(N, H, W, device) to
+    reuse; by default one is allocated.  Views whose rows are dense are read in place through their strides; any other layout
+    is copied once."""
+    who = "fit_pose"
+    if flow is None:
+        raise DvsError("%s: flow: a measured flow [N,2,H,W] is what the pose is fitted to" % who)
+    N, H, W = _rigid_args(who, depth, T0, K, inv_K, flow, valid, T_name="T0" if T0 is not None else None)
+    iters = int(iters)
+    if not 0 <= iters <= 64:
+        raise DvsError("%s: iters=%r must be in 0 .. 64" % (who, iters))
+    huber = float(huber)
+    if not huber > 0.0:
+        raise DvsError("%s: huber=%r must be above 0 (inf: plain least squares)" % (who, huber))
+    damping, eps = not_negative(who, damping=damping, eps=eps)
+    d, d_image, d_row = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
+    mat = lambda m: m.detach().expand(N, 4, 4).contiguous()
+    K = mat(K)
+    inv_K = mat(inv_K) if inv_K is not None else torch.linalg.inv(K).contiguous()
+    T0 = mat(T0) if T0 is not None else torch.eye(4, device=d.device, dtype=torch.float32).repeat(N, 1, 1)
+    f, f_image, f_plane, f_row = _rows(flow.detach())
+    valid = valid.contiguous() if valid is not None else None
+    lib = _lib.lib()
+    need = int(lib.dvs_pose_fit_workspace(N, H, W))
+    if workspace is None:
+        workspace = torch.empty((need,), device=d.device, dtype=torch.uint8)
+    elif workspace.device != d.device or workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise DvsError("%s: workspace must be a dense tensor of at least %d bytes on %s" % (who, need, d.device))
+    T = torch.empty((N, 4, 4), device=d.device, dtype=torch.float32)
+    status = torch.empty((N,), device=d.device, dtype=torch.int32)
+    sums = torch.empty((N, POSE_SUMS), device=d.device, dtype=torch.float64) if normal else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    check(lib.dvs_pose_fit(d.data_ptr(), d_image, d_row, K.data_ptr(), inv_K.data_ptr(), T0.data_ptr(), f.data_ptr(), f_image, f_plane,
+                           f_row, p(valid), T.data_ptr(), status.data_ptr(), p(sums), workspace.data_ptr(),
+                           workspace.numel() * workspace.element_size(), N, H, W, iters, huber, damping, eps, _lib.stream()),
+          "dvs_pose_fit")
+    return (T, status, sums) if normal else (T, status)
 
 
 class InputPadder:
@@ -319,13 +381,17 @@ class FlowFrame:
     valid uint8 [N,H,W] on the previous frame's grid and valid_bw on the current frame's (flow_consistency of flow_up and
     flow_up_bw), and with host=True valid_host; they are None otherwise.  flow_low, flow_up and image are the forward pair's.
     A rigid stream (RigidFlowStream) also fills rigid fp32 [N,2,H,W] and motion uint8 [N,H,W] (rigid_flow's rigid and label for
-    flow_up), and with host=True motion_host; they are None otherwise."""
+    flow_up), and with host=True motion_host; they are None otherwise.
+    A pose stream (PoseFlowStream) also fills T fp32 [N,4,4], the camera motion fitted to flow_up (previous -> current camera), and
+    pose_status int32 [N] (fit_pose's status of the last round), and with host=True T_host; rigid and motion are then taken under
+    that T.  They are None otherwise."""
 
     def __init__(self, flow_low, flow_up, image, slot=None, flow_low_bw=None, flow_up_bw=None, valid=None, valid_bw=None,
-                 rigid=None, motion=None):
+                 rigid=None, motion=None, T=None, pose_status=None):
         self.flow_low, self.flow_up, self.image, self._slot = flow_low, flow_up, image, slot
         self.flow_low_bw, self.flow_up_bw, self.valid, self.valid_bw = flow_low_bw, flow_up_bw, valid, valid_bw
         self.rigid, self.motion = rigid, motion
+        self.T, self.pose_status = T, pose_status
 
     def wait(self):
         if self._slot is None:
@@ -341,6 +407,7 @@ class FlowFrame:
     image_host = property(lambda self: self._host("image"))
     valid_host = property(lambda self: self._host("valid"))
     motion_host = property(lambda self: self._host("motion"))
+    T_host = property(lambda self: self._host("T") if "T" in self.wait()._slot else None)
 
 
 class FlowStream:
@@ -421,9 +488,16 @@ class FlowStream:
         if self.image:
             frame.image = flow_to_image(frame.flow_up, convert_to_bgr=self.convert_to_bgr)
         if self.rigid:                                      # on the same un-padded view, masked by the forward validity
-            frame.rigid, frame.motion = rigid_flow(*geo, flow=frame.flow_up, valid=frame.valid, alpha=self.rigid_alpha,
-                                                   beta=self.rigid_beta)
+            self._label(frame, geo)
         return frame, kept
+
+    def _label(self, frame, geo):
+        """A rigid stream's fields of the pair, from its (depth, T, K, inv_K)."""
+        frame.rigid, frame.motion = rigid_flow(*geo, flow=frame.flow_up, valid=frame.valid, alpha=self.rigid_alpha, beta=self.rigid_beta)
+
+    def _host_fields(self, frame):
+        """What host=True copies besides flow_low, image, valid and motion: name -> tensor."""
+        return {}
 
     def _graph_step(self):
         """What the graph holds: s_frame -> a FlowFrame, flow_init and the previous slot advanced in place."""
@@ -500,7 +574,8 @@ class FlowStream:
         if self.use_graph:                                  # `out` is the graph's own frame: every push hands out a fresh one
             out = copy.copy(out)
         if self.host:
-            out._slot = self._ring.put(flow_low=out.flow_low, image=out.image, valid=out.valid, motion=out.motion)
+            out._slot = self._ring.put(flow_low=out.flow_low, image=out.image, valid=out.valid, motion=out.motion,
+                                       **self._host_fields(out))
         return out
 
     def _geo_args(self, frames, depth, T, K, inv_K):
@@ -570,3 +645,60 @@ class RigidFlowStream(FlowStream):
         super().__init__(model, *args, **kw)
         self.rigid = bool(rigid)
         self.rigid_alpha, self.rigid_beta = not_negative("FlowStream", rigid_alpha=rigid_alpha, rigid_beta=rigid_beta)
+
+
+class PoseFlowStream(RigidFlowStream):
+    """RigidFlowStream that FITS the camera motion to the measured flow instead of being handed it: every pair needs only the
+    previous frame's depth and the intrinsics, and its static / moving label is taken under the pose that the static pixels
+    themselves agree on (fit_pose, dvs_pose_fit).
+
+        stream = PoseFlowStream(model, iters=12, bidirectional=True)        # every RigidFlowStream argument, plus pose_iters,
+        for frame in frames:                                                # pose_huber, pose_rounds
+            r = stream.push(frame, depth=depth_prev, K=K, inv_K=inv_K)      # T=: an optional initial guess (PoseNet's); else identity
+            # r.T [N,4,4] previous -> current camera, r.pose_status int32 [N], r.rigid and r.motion under r.T; host=True: r.T_host
+
+    Round 1 fits over `valid` (every pixel in a one-directional stream), pose_iters Gauss-Newton steps with Huber weights of
+    pose_huber pixels.  Every further round labels the flow with rigid_flow under the current pose and refits over the pixels
+    labelled static (label == 1), starting from that pose: a moving object pulls a Huber fit, and leaves the second round
+    altogether.  The frame's rigid and motion are rigid_flow under the final pose, with `valid` as the mask.
+    graph=True: all of it is nodes of the same single-stream graph; the workspace and the static guess are allocated with the
+    other static buffers, and the guess is refilled before every replay (with the identity when none is passed)."""
+
+    def __init__(self, model, *args, pose_iters=4, pose_huber=1.0, pose_rounds=2, **kw):
+        super().__init__(model, *args, **kw)
+        self.pose_iters, self.pose_rounds, self.pose_huber = int(pose_iters), int(pose_rounds), float(pose_huber)
+        if not 1 <= self.pose_iters <= 64 or self.pose_rounds < 1 or not self.pose_huber > 0.0:
+            raise DvsError("FlowStream: pose_iters=%r must be in 1 .. 64, pose_rounds=%r at least 1, pose_huber=%r above 0"
+                           % (pose_iters, pose_rounds, pose_huber))
+        self._pose_ws, self._eye = None, None
+
+    def push(self, frame, depth=None, K=None, inv_K=None, T=None):
+        if T is None and self.rigid and torch.is_tensor(frame) and frame.dim() in (3, 4):
+            N = frame.shape[0] if frame.dim() == 4 else 1
+            device = next(self.model.parameters()).device
+            if self._eye is None or self._eye.shape[0] != N or self._eye.device != device:
+                self._eye = torch.eye(4, device=device, dtype=torch.float32).repeat(N, 1, 1)
+            T = self._eye
+        return super().push(frame, depth=depth, T=T, K=K, inv_K=inv_K)
+
+    def _allocate(self, frames, padder):
+        N, H, W = frames.shape[:3]
+        self._pose_ws = pose_fit_workspace(N, H, W, frames.device) if self.rigid else None
+        super()._allocate(frames, padder)
+
+    def _label(self, frame, geo):
+        depth, T, K, inv_K = geo
+        ws = self._pose_ws if self.use_graph else None      # eager: fresh tensors, a workspace included
+        mask = frame.valid
+        for round_ in range(self.pose_rounds):
+            if round_:                                      # the pixels that are static under the pose so far
+                _, label = rigid_flow(depth, T, K, inv_K, flow=frame.flow_up, valid=frame.valid, alpha=self.rigid_alpha,
+                                      beta=self.rigid_beta)
+                mask = (label == 1).view(torch.uint8)
+            T, frame.pose_status = fit_pose(depth, frame.flow_up, K, inv_K, T0=T, valid=mask, iters=self.pose_iters,
+                                            huber=self.pose_huber, workspace=ws)
+        frame.T = T
+        super()._label(frame, (depth, T, K, inv_K))
+
+    def _host_fields(self, frame):
+        return {"T": frame.T} if self.rigid else {}

@@ -995,6 +995,63 @@ int dvs_rigid_flow(const float* depth, long long depth_image_stride, long long d
                    const unsigned char* valid, float* rigid, float* excess, unsigned char* label, int N, int H, int W, float alpha,
                    float beta, float eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (added under ABI 12: new entry points only) Camera pose from a measured flow and the depth of its source frame
+ *     the inverse of dvs_rigid_flow: the T under which a static scene of this depth shows this flow.  A dense reprojection-error
+ *     Gauss-Newton fit on SE(3) with Huber weights (iteratively re-weighted least squares), the per-pair form of the reference's
+ *     CPU back end (slam/optimizer.py:222-319: g2o, EdgeProjectD3VO under RobustKernelHuber)
+ *
+ *   depth, K, inv_K, flow, valid: as dvs_rigid_flow (depth and flow through their strides, valid dense uint8 or NULL); flow is
+ *   required.  T0: fp32 [N][4][4], the initial guess; T: fp32 [N][4][4], the fit (T may be exactly T0: fitted in place).
+ *   status: int [N], 0 where every iteration took its step, 1 otherwise.  normal (optional): double [N][30], the sums at the final
+ *   T.  workspace: dvs_pose_fit_workspace(N, H, W) bytes, 8-byte aligned, holds nothing between calls.
+ *   ACCUMULATE, one launch for all N images.  In fp32, every operation rounded on its own (no contraction), in exactly this order,
+ *   iK = inv_K, per pixel (x, y), d = depth, (fu, fv) = flow:
+ *       rx = (iK[0][0]*x + iK[0][1]*y) + iK[0][2]                ry, rz: rows 1, 2
+ *       X = d*rx, Y = d*ry, Z = d*rz
+ *       qx = ((T[0][0]*X + T[0][1]*Y) + T[0][2]*Z) + T[0][3]     qy, qz: rows 1, 2
+ *       cx = ((K[0][0]*qx + K[0][1]*qy) + K[0][2]*qz) + K[0][3]  cy, cz: rows 1, 2
+ *       den = cz + eps
+ *       px = cx / den, py = cy / den                             (the correctly rounded quotient)
+ *       tx = x + fu, ty = y + fv                                 (the measured target)
+ *       ex = px - tx, ey = py - ty                               (the residual)
+ *       judged = d finite and d > 0, fu and fv finite, valid NULL or non-zero, cz > 0, 0 <= tx <= W-1, 0 <= ty <= H-1 (closed),
+ *                ex and ey finite
+ *       e2 = ex*ex + ey*ey
+ *       w  = 1 if e2 <= huber*huber, else huber / sqrt(e2)       (sqrt and quotient correctly rounded; huber = +inf: w = 1)
+ *       A[r][k] = (K[r][k] - p_r*K[2][k]) / den                  r = 0, 1 with p_0 = px, p_1 = py;  k = 0, 1, 2
+ *       J[r] = (A[r][0], A[r][1], A[r][2], A[r][2]*qy - A[r][1]*qz, A[r][0]*qz - A[r][2]*qx, A[r][1]*qx - A[r][0]*qy)
+ *     J is the derivative of (px, py) for a left perturbation T <- exp(xi) T, xi = (nu, omega), translation first.  Every judged
+ *     pixel gives one fp32 term to each of 30 sums; the term is widened and ADDED IN fp64:
+ *       sum[idx(i, j)] += w * (J[0][i]*J[0][j] + J[1][i]*J[1][j])    0 <= i <= j < 6; idx counts the upper triangle row by row: 0 .. 20
+ *       sum[21 + i]    += w * (J[0][i]*ex + J[1][i]*ey)              i < 6
+ *       sum[27] += w * e2,  sum[28] += w,  sum[29] += 1              (the cost, the weights, the judged count)
+ *     A lane owns four consecutive pixels of a row (16-byte loads where W, every stride and every pointer allow, single elements
+ *     otherwise) and walks the image with a grid stride; the workgroups per image depend on (H, W) alone.  A 64-lane butterfly,
+ *     the four waves through LDS, one row of 30 doubles per workgroup into the workspace.  No atomics, no memset: the sums repeat
+ *     bit for bit, in both load forms, and an image's sums do not depend on the other images of the batch.
+ *   UPDATE, one launch, one workgroup per image, fp64 (no contraction): the rows are staged in LDS and added in row order, H and g are sums 0 .. 20 and
+ *   21 .. 26,
+ *       A = H + damping * diag(H);  A = L L^T (Cholesky);  L y = -g;  L^T xi = y
+ *       theta2 = (wx*wx + wy*wy) + wz*wz with omega = (wx, wy, wz), W = [omega]x
+ *       theta2 <  1e-4: a = (1 - theta2/6) + theta2^2/120, b = (1/2 - theta2/24) + theta2^2/720, c = (1/6 - theta2/120) + theta2^2/5040
+ *       otherwise:      a = sin(theta)/theta, b = (1 - cos(theta))/theta2, c = (theta - sin(theta))/(theta2*theta)
+ *       R = (I + a W) + b W^2,  V = (I + b W) + c W^2,  t = V nu;  T <- [R t; 0 1] T, rounded to fp32
+ *     The step is SKIPPED for an image -- T keeps its bits for this and every later iteration of the call, status = 1 -- when
+ *     fewer than 6 pixels were judged, a sum, xi or the new T is not finite, or a pivot of the Cholesky is not positive.
+ *   The entry issues `iters` (accumulate, update) pairs; with `normal` one more accumulate at the final T, whose ordered sums are
+ *   stored there (iters = 0: the sums at T0; T = T0, status = 0).
+ *   N, H, W, strides and alignment as dvs_rigid_flow; 0 <= iters <= 64; huber > 0 (+inf allowed, NaN not); damping and eps finite
+ *   and >= 0; workspace_bytes >= dvs_pose_fit_workspace (0 for a shape the entry refuses); T and status 4-byte, normal and workspace
+ *   8-byte aligned; no output may overlap an input or another output, except T == T0.  DVS_ERR_INVALID, before any launch, otherwise.
+ *   Only `stream` is used; dvs_set_precision does not affect this entry.
+ * ------------------------------------------------------------------------------------------- */
+size_t dvs_pose_fit_workspace(int N, int H, int W);
+int dvs_pose_fit(const float* depth, long long depth_image_stride, long long depth_row_stride, const float* K, const float* inv_K,
+                 const float* T0, const float* flow, long long flow_image_stride, long long flow_plane_stride, long long flow_row_stride,
+                 const unsigned char* valid, float* T, int* status, double* normal, void* workspace, size_t workspace_bytes, int N, int H,
+                 int W, int iters, float huber, float damping, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
