@@ -9,7 +9,9 @@
 #define DVS_TIMING_EXPERIMENTS 0
 #endif
 
+#include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
@@ -42,6 +44,10 @@ inline int check_launch(const char* what) {
     do {                       \
         if (!(cond)) return dvs::fail(DVS_ERR_INVALID, __VA_ARGS__); \
     } while (0)
+
+// what the entry points ask of a pointer (`a` a power of two; null is aligned) and of a threshold
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline bool finite_nonneg(float v) { return v >= 0.0f && v < INFINITY; }
 
 // ---- per-kernel timing with HIP events on the launch stream (include/dvslam.h: dvs_profile_*)
 enum ProfSlot { SLOT_CHAIN_FWD = 0, SLOT_CHAIN_BWD, SLOT_ADAM, SLOT_CONV_FWD, SLOT_CONV_DGRAD, SLOT_CONV_WGRAD,
@@ -84,6 +90,12 @@ constexpr int kWave = 64;  // gfx950 wavefront
 
 // 64-lane butterfly sum; every lane ends with the total.
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// the same in fp64 (two dwords a shuffle), in one fixed order
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

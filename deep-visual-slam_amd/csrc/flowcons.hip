@@ -18,28 +18,19 @@
 // as in flowstage.hip and ingest.hip.  The border is closed, so a zero flow is valid on the whole image; a clamped tap (x1 = x0 at
 // qx = W-1) carries weight 0, and a pixel that is not inside reads nothing of the partner: no address outside the two views is formed.
 //
-// A streaming kernel at the launch floor: a lane owns four consecutive pixels of a row, the direction rides in blockIdx.z and the
-// image in blockIdx.y.  VEC: the lane's own flow is two 16-byte loads, its four mask bytes one dword store and its excess one
-// 16-byte store (W, the own flow's strides and every pointer involved are multiples of 4 elements / aligned accordingly); the
-// scalar form loads and stores single elements.  The sixteen taps of the partner are scalar gathers in both forms.  No LDS, no
-// atomics, no workspace; every output element is written once by the lane that owns it, so the result repeats bit for bit and
-// does not depend on the launch geometry.
-#include "common.h"
-
-#include <cmath>
-#include <cstdint>
+// A streaming kernel at the launch floor, in the lane geometry of pixelfield.h (a lane owns four consecutive pixels of a row), the
+// direction in blockIdx.z and the image in blockIdx.y.  The lane's own flow, its mask bytes and its excess go through pixelfield.h's
+// vector or scalar loads and stores; the sixteen taps of the partner are scalar gathers in both forms.  No LDS, no atomics, no
+// workspace; every output element is written once by the lane that owns it, so the result repeats bit for bit and does not
+// depend on the launch geometry.
+#include "pixelfield.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPix = 4;                             // pixels per lane: four mask bytes = one dword, four excess values = 16 bytes
-
-struct Field {                                      // one flow, element strides: u of (n, y, x) at p[n * image + y * row + x], v one plane on
-    const float* p;
-    long long image, plane, row;
-};
+using namespace dvs;
+constexpr int kThreads = kPixThreads;
 
 struct Pair {
     Field flow[2];                                  // [0] = a, [1] = b
@@ -63,7 +54,7 @@ __device__ __forceinline__ float excess_of(const Field& o, const float* __restri
                                            float av, float alpha, float beta) {
     const float qx = (float)x + au, qy = (float)y + av;
     const bool inside = qx >= 0.0f && qx <= (float)(W - 1) && qy >= 0.0f && qy <= (float)(H - 1);
-    if (!inside) return INFINITY;
+    if (!inside) return INFINITY;                                     // NaN included: a pixel past the row's tail reads nothing
     const float fx = floorf(qx), fy = floorf(qy);
     const int x0 = (int)fx, y0 = (int)fy;                             // 0 .. W - 1, 0 .. H - 1
     const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
@@ -81,71 +72,27 @@ __device__ __forceinline__ float excess_of(const Field& o, const float* __restri
 
 template <bool VEC>
 __global__ void __launch_bounds__(kThreads) flow_consistency_kernel(Pair s) {
-    const unsigned g = blockIdx.x * kThreads + threadIdx.x;           // host: H * quads < 2^31 - kThreads
-    const unsigned y = g / (unsigned)s.quads;
+    unsigned y;
+    int x;
+    lane_pixels(blockIdx.x * kThreads + threadIdx.x, s.quads, &y, &x);
     if (y >= (unsigned)s.H) return;
-    const int x = (int)(g - y * (unsigned)s.quads) * kPix;
-    const int n = blockIdx.y, dir = blockIdx.z;
+    const int n = blockIdx.y, dir = blockIdx.z, count = s.W - x;
     const Field own = s.flow[dir], oth = s.flow[dir ^ 1];
-    unsigned char* __restrict__ valid = s.valid[dir];
-    float* __restrict__ excess = s.excess[dir];
-    const float* mine = own.p + (size_t)n * (size_t)own.image + (size_t)y * (size_t)own.row + x;
-    const float* other = oth.p + (size_t)n * (size_t)oth.image;
-    float u[kPix], v[kPix];
-    if (VEC) {                                                        // W % 4 == 0: the four are in the row, 16-byte aligned
-        const float4 a = *reinterpret_cast<const float4*>(mine), b = *reinterpret_cast<const float4*>(mine + own.plane);
-        u[0] = a.x, u[1] = a.y, u[2] = a.z, u[3] = a.w;
-        v[0] = b.x, v[1] = b.y, v[2] = b.z, v[3] = b.w;
-    } else {
+    const float* mine = at(own, n, y, x);
+    const float* other = at(oth, n, 0, 0);
+    float u[kPix], v[kPix], e[kPix];
+    load_quad<VEC>(mine, count, u);
+    load_quad<VEC>(mine + own.plane, count, v);
+    unsigned m = 0;
 #pragma unroll
-        for (int k = 0; k < kPix; ++k) {
-            u[k] = v[k] = NAN;                                        // past the row: not inside, nothing is read for it
-            if (x + k < s.W) u[k] = mine[k], v[k] = mine[own.plane + k];
-        }
+    for (int k = 0; k < kPix; ++k) {
+        e[k] = excess_of(oth, other, x + k, (int)y, s.H, s.W, u[k], v[k], s.alpha, s.beta);
+        m |= (e[k] <= 0.0f ? 1u : 0u) << (8 * k);
     }
-    float e[kPix];
-#pragma unroll
-    for (int k = 0; k < kPix; ++k) e[k] = excess_of(oth, other, x + k, (int)y, s.H, s.W, u[k], v[k], s.alpha, s.beta);
     const size_t o = ((size_t)n * (size_t)s.H + y) * (size_t)s.W + x;
-    if (VEC) {
-        if (valid) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < kPix; ++k) m |= (e[k] <= 0.0f ? 1u : 0u) << (8 * k);
-            *reinterpret_cast<unsigned*>(valid + o) = m;
-        }
-        if (excess) *reinterpret_cast<float4*>(excess + o) = make_float4(e[0], e[1], e[2], e[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPix; ++k) {
-            if (x + k < s.W) {                                        // the row's tail
-                if (valid) valid[o + k] = e[k] <= 0.0f ? 1 : 0;
-                if (excess) excess[o + k] = e[k];
-            }
-        }
-    }
+    if (s.valid[dir]) store_mask<VEC>(s.valid[dir] + o, count, m);
+    if (s.excess[dir]) store_quad<VEC>(s.excess[dir] + o, count, e);
 }
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-int make_field(const char* name, const float* p, long long image, long long plane, long long row, int H, int W, Field* f) {
-    DVS_REQUIRE(p, "dvs_flow_consistency: null pointer (%s)", name);
-    DVS_REQUIRE(aligned(p, 4), "dvs_flow_consistency: misaligned pointer (%s)", name);
-    DVS_REQUIRE(row >= W, "dvs_flow_consistency: %s row stride %lld is below W=%d", name, row, W);
-    DVS_REQUIRE(row < (1ll << 40) && plane < (1ll << 40) && image < (1ll << 40), "dvs_flow_consistency: %s strides %lld, %lld, %lld out of range",
-                name, image, plane, row);
-    const long long extent = (long long)(H - 1) * row + W;
-    DVS_REQUIRE(plane >= extent, "dvs_flow_consistency: %s plane stride %lld is below (H - 1) * row stride + W = %lld", name, plane, extent);
-    DVS_REQUIRE(image >= plane + extent, "dvs_flow_consistency: %s image stride %lld is below plane stride + (H - 1) * row stride + W = %lld",
-                name, image, plane + extent);
-    f->p = p;
-    f->image = image;
-    f->plane = plane;
-    f->row = row;
-    return DVS_OK;
-}
-
-bool vec_field(const Field& f) { return f.row % 4 == 0 && f.plane % 4 == 0 && f.image % 4 == 0 && aligned(f.p, 16); }
 
 }  // namespace
 
@@ -155,31 +102,29 @@ int dvs_flow_consistency(const float* a, long long a_image_stride, long long a_p
                          long long b_image_stride, long long b_plane_stride, long long b_row_stride, unsigned char* valid_a,
                          unsigned char* valid_b, float* excess_a, float* excess_b, int N, int H, int W, float alpha, float beta,
                          void* stream) {
-    DVS_REQUIRE(N >= 1 && N <= 65535, "dvs_flow_consistency: N=%d images must be in 1 .. 65535", N);
-    DVS_REQUIRE(H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24),
-                "dvs_flow_consistency: H=%d, W=%d must be in 1 .. 2^24 (pixel coordinates are exact in fp32)", H, W);
-    const long long quads = ((long long)W + kPix - 1) / kPix;
-    DVS_REQUIRE((long long)H * quads < (1ll << 31) - kThreads, "dvs_flow_consistency: H * W = %d x %d pixels per image exceed 2^31 - 1 lanes of four",
-                H, W);
+    const char* who = "dvs_flow_consistency";
     Pair s;
-    if (int rc = make_field("a", a, a_image_stride, a_plane_stride, a_row_stride, H, W, &s.flow[0])) return rc;
-    if (int rc = make_field("b", b, b_image_stride, b_plane_stride, b_row_stride, H, W, &s.flow[1])) return rc;
-    DVS_REQUIRE(alpha >= 0.0f && beta >= 0.0f && alpha < INFINITY && beta < INFINITY,
-                "dvs_flow_consistency: alpha=%g, beta=%g must be finite and not negative", (double)alpha, (double)beta);
+    if (int rc = check_shape(who, N, H, W, &s.quads)) return rc;
+    s.flow[0] = Field{a, a_image_stride, a_plane_stride, a_row_stride};
+    s.flow[1] = Field{b, b_image_stride, b_plane_stride, b_row_stride};
+    if (int rc = check_field(who, "a", s.flow[0], H, W)) return rc;
+    if (int rc = check_field(who, "b", s.flow[1], H, W)) return rc;
+    DVS_REQUIRE(finite_nonneg(alpha) && finite_nonneg(beta), "dvs_flow_consistency: alpha=%g, beta=%g must be finite and not negative",
+                (double)alpha, (double)beta);
     DVS_REQUIRE(aligned(excess_a, 4) && aligned(excess_b, 4), "dvs_flow_consistency: misaligned pointer (excess)");
     s.valid[0] = valid_a, s.valid[1] = valid_b;
     s.excess[0] = excess_a, s.excess[1] = excess_b;
-    s.H = H, s.W = W, s.quads = (int)quads;
+    s.H = H, s.W = W;
     s.alpha = alpha, s.beta = beta;
     if (!valid_a && !valid_b && !excess_a && !excess_b) return DVS_OK;            // nothing to write: no launch
-    const bool vec = W % 4 == 0 && vec_field(s.flow[0]) && vec_field(s.flow[1]) && aligned(valid_a, 4) && aligned(valid_b, 4) &&
-                     aligned(excess_a, 16) && aligned(excess_b, 16);
-    const unsigned lanes = (unsigned)H * (unsigned)quads;
+    const bool vector = W % 4 == 0 && vec(s.flow[0]) && vec(s.flow[1]) && aligned(valid_a, 4) && aligned(valid_b, 4) &&
+                        aligned(excess_a, 16) && aligned(excess_b, 16);
+    const unsigned lanes = (unsigned)H * (unsigned)s.quads;
     const dim3 grid((lanes + kThreads - 1) / kThreads, (unsigned)N, 2);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(flow_consistency_kernel<true>, grid, dim3(kThreads), 0, st, s);
+    if (vector) hipLaunchKernelGGL(flow_consistency_kernel<true>, grid, dim3(kThreads), 0, st, s);
     else hipLaunchKernelGGL(flow_consistency_kernel<false>, grid, dim3(kThreads), 0, st, s);
-    return dvs::check_launch("dvs_flow_consistency");
+    return check_launch(who);
 }
 
 }  // extern "C"

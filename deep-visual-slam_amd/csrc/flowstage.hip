@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(kThreads) flow_to_image_kernel(View s, const f
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using dvs::aligned;
 
 int make_view(const char* who, const float* flow, long long plane_stride, long long row_stride, int N, int H, int W, float clip_flow,
               View* s, bool* vec) {

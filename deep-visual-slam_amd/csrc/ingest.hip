@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(kThreads) frame_ingest_kernel(Frame f, float* 
         if (x0 + k < f.Wp) o[k] = normalised(rgb[k], f.bgr);          // the row's tail, not the border
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using dvs::aligned;
 
 }  // namespace
 

@@ -8,8 +8,7 @@
 // ACCUMULATE (one launch for all N images).  Per pixel (x, y), d = depth, (fu, fv) = flow, iK = inv_K, fp32, every operation
 // rounded on its own (contraction is off for the whole file):
 //
-//   rx = (iK[0][0]*x + iK[0][1]*y) + iK[0][2]                ry, rz: rows 1, 2          as dvs_rigid_flow
-//   X = d*rx, Y = d*ry, Z = d*rz
+//   (X, Y, Z) = d * (rx, ry, rz)                             the ray of pixelfield.h, as dvs_rigid_flow
 //   qx = ((T[0][0]*X + T[0][1]*Y) + T[0][2]*Z) + T[0][3]     qy, qz: rows 1, 2
 //   cx = ((K[0][0]*qx + K[0][1]*qy) + K[0][2]*qz) + K[0][3]  cy, cz: rows 1, 2
 //   den = cz + eps;  px = cx / den, py = cy / den            the correctly rounded quotient
@@ -27,7 +26,7 @@
 //   sum[21 + i]    += w * (J[0][i]*ex + J[1][i]*ey)                i < 6
 //   sum[27] += w * e2;   sum[28] += w;   sum[29] += 1
 //
-// A lane owns four consecutive pixels of a row (VEC: 16-byte loads under rigidflow.hip's alignment rule, else single elements) and
+// A lane owns four consecutive pixels of a row (pixelfield.h: its lane geometry, its views, its vector or scalar loads) and
 // walks the image with a grid stride; the number of workgroups per image depends on (H, W) alone.  30 fp64 accumulators a lane,
 // a 64-lane butterfly of shuffles, the four waves through LDS, and ONE row of 30 doubles per workgroup into the workspace.
 // There are no atomics and no memset: the sums repeat bit for bit and an image's sums do not depend on the rest of the batch.
@@ -43,27 +42,22 @@
 //
 // The step is skipped -- T keeps its bits for this and every later iteration, status = 1 -- when fewer than 6 pixels were judged,
 // a sum, xi or the new T is not finite, or a pivot is not positive.
-#include "common.h"
-
-#include <cmath>
-#include <cstdint>
+#include "pixelfield.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPix = 4;                             // pixels per lane, as rigidflow.hip
+using namespace dvs;
+constexpr int kThreads = kPixThreads;
 constexpr int kSums = 30;                           // 21 of J^T J, 6 of J^T e, the cost, the weights, the count
-constexpr int kWaves = kThreads / dvs::kWave;
+constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxGroups = 256;                     // workgroups per image at the most: rows the update adds one after another
 
 struct Args {
-    const float* depth;                             // d of (n, y, x) at depth[n * d_image + y * d_row + x]
-    long long d_image, d_row;
+    Plane depth;
     const float *K, *iK, *T;                        // dense [N][4][4]
-    const float* flow;                              // u of (n, y, x) at flow[n * f_image + y * f_row + x], v one plane on
-    long long f_image, f_plane, f_row;
+    Field flow;
     const unsigned char* valid;                     // dense [N][H][W], may be null
     double* partial;                                // [N][groups][kSums]
     int H, W;
@@ -79,15 +73,12 @@ struct Camera {
 __device__ __forceinline__ Camera camera_of(const Args& s, int n) {
     const float* __restrict__ K = s.K + (size_t)n * 16;
     const float* __restrict__ T = s.T + (size_t)n * 16;
-    const float* __restrict__ iK = s.iK + (size_t)n * 16;
     Camera c;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) c.K[i][j] = K[4 * i + j], c.T[i][j] = T[4 * i + j];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.iK[i][j] = iK[4 * i + j];
-    }
+    load_inv_K(s.iK + (size_t)n * 16, c.iK);
     return c;
 }
 
@@ -95,10 +86,8 @@ __device__ __forceinline__ Camera camera_of(const Args& s, int n) {
 __device__ __forceinline__ void pixel(const Camera& c, int xi, int yi, float d, float fu, float fv, bool ok, int H, int W, float eps,
                                       float huber, float huber2, double (&acc)[kSums]) {
     const float x = (float)xi, y = (float)yi;
-    const float rx = (c.iK[0][0] * x + c.iK[0][1] * y) + c.iK[0][2];
-    const float ry = (c.iK[1][0] * x + c.iK[1][1] * y) + c.iK[1][2];
-    const float rz = (c.iK[2][0] * x + c.iK[2][1] * y) + c.iK[2][2];
-    const float X = d * rx, Y = d * ry, Z = d * rz;
+    float X, Y, Z;
+    back_project(c.iK, x, y, d, &X, &Y, &Z);
     const float qx = ((c.T[0][0] * X + c.T[0][1] * Y) + c.T[0][2] * Z) + c.T[0][3];
     const float qy = ((c.T[1][0] * X + c.T[1][1] * Y) + c.T[1][2] * Z) + c.T[1][3];
     const float qz = ((c.T[2][0] * X + c.T[2][1] * Y) + c.T[2][2] * Z) + c.T[2][3];
@@ -139,13 +128,6 @@ __device__ __forceinline__ void pixel(const Camera& c, int xi, int yi, float d, 
     acc[29] += 1.0;
 }
 
-// 64-lane butterfly in fp64 (two dwords a shuffle); every lane ends with the total, in one fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool VEC>
 __global__ void __launch_bounds__(kThreads) pose_fit_accumulate(Args s) {
     __shared__ double part[kWaves][kSums];
@@ -157,39 +139,25 @@ __global__ void __launch_bounds__(kThreads) pose_fit_accumulate(Args s) {
     for (int i = 0; i < kSums; ++i) acc[i] = 0.0;
     const unsigned stride = gridDim.x * kThreads;                     // host: lanes < 2^31 - kThreads, stride <= 2^16
     for (unsigned g = blockIdx.x * kThreads + threadIdx.x; g < s.lanes; g += stride) {
-        const unsigned y = g / (unsigned)s.quads;
-        const int x = (int)(g - y * (unsigned)s.quads) * kPix;
-        const float* dp = s.depth + (size_t)n * (size_t)s.d_image + (size_t)y * (size_t)s.d_row + x;
-        const float* fp = s.flow + (size_t)n * (size_t)s.f_image + (size_t)y * (size_t)s.f_row + x;
+        unsigned y;
+        int x;
+        lane_pixels(g, s.quads, &y, &x);
+        const int count = s.W - x;
+        const float* fp = at(s.flow, n, y, x);
         const size_t o = ((size_t)n * (size_t)s.H + y) * (size_t)s.W + x;             // of the dense valid [N][H][W]
         float d[kPix], fu[kPix], fv[kPix];
-        unsigned ok = 0x01010101u;                                    // the four valid bytes; all judged without a mask
-        if (VEC) {                                                    // W % 4 == 0: the four are in the row, 16-byte aligned
-            const float4 a = *reinterpret_cast<const float4*>(dp);
-            const float4 b = *reinterpret_cast<const float4*>(fp), c = *reinterpret_cast<const float4*>(fp + s.f_plane);
-            d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w;
-            fu[0] = b.x, fu[1] = b.y, fu[2] = b.z, fu[3] = b.w;
-            fv[0] = c.x, fv[1] = c.y, fv[2] = c.z, fv[3] = c.w;
-            if (s.valid) ok = *reinterpret_cast<const unsigned*>(s.valid + o);
-        } else {
-            ok = 0;
-#pragma unroll
-            for (int k = 0; k < kPix; ++k) {
-                d[k] = fu[k] = fv[k] = NAN;                           // past the row: nothing is read for it, and it is not judged
-                if (x + k < s.W) {
-                    d[k] = dp[k], fu[k] = fp[k], fv[k] = fp[s.f_plane + k];
-                    ok |= (s.valid ? (s.valid[o + k] ? 1u : 0u) : 1u) << (8 * k);
-                }
-            }
-        }
+        load_quad<VEC>(at(s.depth, n, y, x), count, d);
+        load_quad<VEC>(fp, count, fu);
+        load_quad<VEC>(fp + s.flow.plane, count, fv);
+        const unsigned ok = load_mask<VEC>(s.valid ? s.valid + o : nullptr, count);
 #pragma unroll
         for (int k = 0; k < kPix; ++k)
             pixel(cam, x + k, (int)y, d[k], fu[k], fv[k], (ok >> (8 * k) & 255u) != 0, s.H, s.W, s.eps, s.huber, huber2, acc);
     }
 #pragma unroll
     for (int i = 0; i < kSums; ++i) acc[i] = wave_sum(acc[i]);
-    const int wave = threadIdx.x / dvs::kWave;
-    if (threadIdx.x % dvs::kWave == 0) {
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) {
 #pragma unroll
         for (int i = 0; i < kSums; ++i) part[wave][i] = acc[i];
     }
@@ -337,32 +305,11 @@ __global__ void __launch_bounds__(kThreads) pose_fit_update(Step u) {
     u.status[n] = st;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-struct Span {                                       // the bytes [lo, hi) an argument covers; empty for a null pointer
-    const char* name;
-    uintptr_t lo, hi;
-};
-
-Span span(const char* name, const void* p, long long bytes) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Span{name, lo, p ? lo + (uintptr_t)bytes : lo};
-}
-
-bool finite_nonneg(float v) { return v >= 0.0f && v < INFINITY; }
-
 // workgroups per image: every workgroup walks the same number of strides, and (H, W) alone decide
-int groups_of(int H, int W) {
-    const long long quads = ((long long)W + kPix - 1) / kPix;
+int groups_of(int H, int quads) {
     const long long blocks = ((long long)H * quads + kThreads - 1) / kThreads;
     const long long walks = (blocks + kMaxGroups - 1) / kMaxGroups;
     return (int)((blocks + walks - 1) / walks);
-}
-
-bool shape_ok(int N, int H, int W) {
-    if (N < 1 || N > 65535 || H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24)) return false;
-    const long long quads = ((long long)W + kPix - 1) / kPix;
-    return (long long)H * quads < (1ll << 31) - kThreads;
 }
 
 }  // namespace
@@ -370,74 +317,47 @@ bool shape_ok(int N, int H, int W) {
 extern "C" {
 
 size_t dvs_pose_fit_workspace(int N, int H, int W) {
-    if (!shape_ok(N, H, W)) return 0;
-    return (size_t)N * (size_t)groups_of(H, W) * kSums * sizeof(double);
+    const int quads = quads_of(N, H, W);
+    return quads ? (size_t)N * (size_t)groups_of(H, quads) * kSums * sizeof(double) : 0;
 }
 
 int dvs_pose_fit(const float* depth, long long depth_image_stride, long long depth_row_stride, const float* K, const float* inv_K,
                  const float* T0, const float* flow, long long flow_image_stride, long long flow_plane_stride, long long flow_row_stride,
                  const unsigned char* valid, float* T, int* status, double* normal, void* workspace, size_t workspace_bytes, int N, int H,
                  int W, int iters, float huber, float damping, float eps, void* stream) {
-    DVS_REQUIRE(N >= 1 && N <= 65535, "dvs_pose_fit: N=%d images must be in 1 .. 65535", N);
-    DVS_REQUIRE(H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24),
-                "dvs_pose_fit: H=%d, W=%d must be in 1 .. 2^24 (pixel coordinates are exact in fp32)", H, W);
-    DVS_REQUIRE(shape_ok(N, H, W), "dvs_pose_fit: H * W = %d x %d pixels per image exceed 2^31 - 1 lanes of four", H, W);
-    const long long quads = ((long long)W + kPix - 1) / kPix;
-    DVS_REQUIRE(depth && K && inv_K && T0 && flow, "dvs_pose_fit: null pointer (depth, K, inv_K, T0 or flow)");
+    const char* who = "dvs_pose_fit";
+    Args s;
+    if (int rc = check_shape(who, N, H, W, &s.quads)) return rc;
+    s.depth = Plane{depth, depth_image_stride, depth_row_stride};
+    s.flow = Field{flow, flow_image_stride, flow_plane_stride, flow_row_stride};
+    if (int rc = check_plane(who, "depth", s.depth, H, W)) return rc;
+    if (int rc = check_floats(who, "K", K)) return rc;
+    if (int rc = check_floats(who, "inv_K", inv_K)) return rc;
+    if (int rc = check_floats(who, "T0", T0)) return rc;
+    if (int rc = check_field(who, "flow", s.flow, H, W)) return rc;
     DVS_REQUIRE(T && status && workspace, "dvs_pose_fit: null pointer (T, status or workspace)");
-    DVS_REQUIRE(aligned(depth, 4) && aligned(K, 4) && aligned(inv_K, 4) && aligned(T0, 4) && aligned(flow, 4),
-                "dvs_pose_fit: misaligned pointer (depth, K, inv_K, T0 or flow)");
     DVS_REQUIRE(aligned(T, 4) && aligned(status, 4) && aligned(normal, 8) && aligned(workspace, 8),
                 "dvs_pose_fit: misaligned pointer (T, status, normal or workspace)");
-    const long long extent = (long long)(H - 1) * depth_row_stride + W;
-    DVS_REQUIRE(depth_row_stride >= W, "dvs_pose_fit: depth row stride %lld is below W=%d", depth_row_stride, W);
-    DVS_REQUIRE(depth_row_stride < (1ll << 40) && depth_image_stride < (1ll << 40), "dvs_pose_fit: depth strides %lld, %lld out of range",
-                depth_image_stride, depth_row_stride);
-    DVS_REQUIRE(depth_image_stride >= extent, "dvs_pose_fit: depth image stride %lld is below (H - 1) * row stride + W = %lld",
-                depth_image_stride, extent);
-    DVS_REQUIRE(flow_row_stride >= W, "dvs_pose_fit: flow row stride %lld is below W=%d", flow_row_stride, W);
-    DVS_REQUIRE(flow_row_stride < (1ll << 40) && flow_plane_stride < (1ll << 40) && flow_image_stride < (1ll << 40),
-                "dvs_pose_fit: flow strides %lld, %lld, %lld out of range", flow_image_stride, flow_plane_stride, flow_row_stride);
-    const long long f_extent = (long long)(H - 1) * flow_row_stride + W;
-    DVS_REQUIRE(flow_plane_stride >= f_extent, "dvs_pose_fit: flow plane stride %lld is below (H - 1) * row stride + W = %lld",
-                flow_plane_stride, f_extent);
-    DVS_REQUIRE(flow_image_stride >= flow_plane_stride + f_extent,
-                "dvs_pose_fit: flow image stride %lld is below plane stride + (H - 1) * row stride + W = %lld", flow_image_stride,
-                flow_plane_stride + f_extent);
     DVS_REQUIRE(iters >= 0 && iters <= 64, "dvs_pose_fit: iters=%d must be in 0 .. 64", iters);
     DVS_REQUIRE(huber > 0.0f, "dvs_pose_fit: huber=%g must be above 0 (+inf: plain least squares)", (double)huber);
     DVS_REQUIRE(finite_nonneg(damping) && finite_nonneg(eps), "dvs_pose_fit: damping=%g, eps=%g must be finite and not negative",
                 (double)damping, (double)eps);
-    const int groups = groups_of(H, W);
+    const int groups = groups_of(H, s.quads);
     const size_t need = (size_t)N * (size_t)groups * kSums * sizeof(double);
     DVS_REQUIRE(workspace_bytes >= need, "dvs_pose_fit: workspace of %zu bytes is below dvs_pose_fit_workspace = %zu", workspace_bytes, need);
     const long long pixels = (long long)N * H * W;
-    const Span ins[] = {span("depth", depth, 4 * ((long long)(N - 1) * depth_image_stride + extent)),
-                        span("K", K, 64ll * N),
-                        span("inv_K", inv_K, 64ll * N),
-                        span("T0", T0, 64ll * N),
-                        span("flow", flow, 4 * ((long long)(N - 1) * flow_image_stride + flow_plane_stride + f_extent)),
-                        span("valid", valid, pixels)};
+    // T may be exactly T0 (fitted in place): T0 then stands for no range of its own, and the other outputs are held against T
+    const Span ins[] = {span("depth", s.depth, N, H, W), span("K", K, 64ll * N), span("inv_K", inv_K, 64ll * N),
+                        span("T0", T == T0 ? nullptr : T0, 64ll * N), span("flow", s.flow, N, H, W), span("valid", valid, pixels)};
     const Span outs[] = {span("T", T, 64ll * N), span("status", status, 4ll * N), span("normal", normal, 8ll * kSums * N),
                          span("workspace", workspace, (long long)need)};
-    for (const Span& o : outs)
-        for (const Span& i : ins) {
-            if (&o == &outs[0] && &i == &ins[3] && T == T0) continue;                      // T may be exactly T0: fitted in place
-            DVS_REQUIRE(!(o.lo < i.hi && i.lo < o.hi), "dvs_pose_fit: output %s overlaps input %s", o.name, i.name);
-        }
-    for (const Span& a : outs)
-        for (const Span& b : outs)
-            DVS_REQUIRE(&a == &b || !(a.lo < b.hi && b.lo < a.hi), "dvs_pose_fit: output %s overlaps output %s", a.name, b.name);
-    Args s;
-    s.depth = depth, s.d_image = depth_image_stride, s.d_row = depth_row_stride;
+    if (int rc = check_overlap(who, outs, ins, "input")) return rc;
+    if (int rc = check_overlap(who, outs, outs, "output")) return rc;
     s.K = K, s.iK = inv_K, s.T = T0;
-    s.flow = flow, s.f_image = flow_image_stride, s.f_plane = flow_plane_stride, s.f_row = flow_row_stride;
     s.valid = valid, s.partial = static_cast<double*>(workspace);
-    s.H = H, s.W = W, s.quads = (int)quads, s.lanes = (unsigned)H * (unsigned)quads;
+    s.H = H, s.W = W, s.lanes = (unsigned)H * (unsigned)s.quads;
     s.huber = huber, s.eps = eps;
-    const bool vec = W % 4 == 0 && depth_row_stride % 4 == 0 && depth_image_stride % 4 == 0 && aligned(depth, 16) &&
-                     flow_row_stride % 4 == 0 && flow_plane_stride % 4 == 0 && flow_image_stride % 4 == 0 && aligned(flow, 16) &&
-                     aligned(valid, 4);
+    const bool vector = W % 4 == 0 && vec(s.depth) && vec(s.flow) && aligned(valid, 4);
     Step u;
     u.partial = s.partial, u.groups = groups, u.Tin = T0, u.Tout = T, u.status = status, u.normal = nullptr;
     u.solve = 1, u.first = 1, u.damping = (double)damping;
@@ -445,11 +365,11 @@ int dvs_pose_fit(const float* depth, long long depth_image_stride, long long dep
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int passes = iters + (normal ? 1 : 0);
     for (int it = 0; it < passes; ++it) {
-        if (vec) hipLaunchKernelGGL(pose_fit_accumulate<true>, grid, dim3(kThreads), 0, st, s);
+        if (vector) hipLaunchKernelGGL(pose_fit_accumulate<true>, grid, dim3(kThreads), 0, st, s);
         else hipLaunchKernelGGL(pose_fit_accumulate<false>, grid, dim3(kThreads), 0, st, s);
         if (it == iters) u.solve = 0, u.normal = normal;              // the last pass of a call that hands the sums out
         hipLaunchKernelGGL(pose_fit_update, dim3((unsigned)N), dim3(kThreads), 0, st, u);
-        const int rc = dvs::check_launch("dvs_pose_fit");
+        const int rc = check_launch(who);
         if (rc != DVS_OK) return rc;
         s.T = u.Tin = T, u.first = 0;
     }
@@ -457,7 +377,7 @@ int dvs_pose_fit(const float* depth, long long depth_image_stride, long long dep
         u.partial = nullptr, u.solve = 0;
         hipLaunchKernelGGL(pose_fit_update, dim3((unsigned)N), dim3(kThreads), 0, st, u);
     }
-    return dvs::check_launch("dvs_pose_fit");
+    return check_launch(who);
 }
 
 }  // extern "C"

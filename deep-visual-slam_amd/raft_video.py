@@ -162,6 +162,18 @@ def _rigid_args(who, depth, T, K, inv_K, flow=None, valid=None, shape=None, T_na
     return N, H, W
 
 
+def _geometry(N, depth, K, inv_K, flow, valid, pose, pose_first):
+    """dvs_rigid_flow's and dvs_pose_fit's operands: depth view, dense [N,4,4] K, inv_K and pose, flow view, dense valid, pointer-or-None."""
+    d = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
+    mat = lambda m: m.detach().expand(N, 4, 4).contiguous()
+    pose, K = (mat(pose) if pose_first else pose), mat(K)       # before K or after inv_K: each caller's own order of copies, kept
+    inv_K = mat(inv_K) if inv_K is not None else torch.linalg.inv(K).contiguous()
+    if not pose_first:                                          # fit_pose: no guess is the identity
+        pose = mat(pose) if pose is not None else torch.eye(4, device=d[0].device, dtype=torch.float32).repeat(N, 1, 1)
+    f = _rows(flow.detach()) if flow is not None else (None, 0, 0, 0)
+    return d, K, inv_K, pose, f, valid.contiguous() if valid is not None else None, lambda t: t.data_ptr() if t is not None else None
+
+
 def rigid_flow(depth, T, K, inv_K=None, flow=None, valid=None, alpha=0.01, beta=0.5, eps=1e-7, excess=False):
     """The flow a STATIC scene shows under this depth and this camera motion, and where a measured flow disagrees with it, on the
     device in ONE launch (dvs_rigid_flow; include/dvslam.h states the arithmetic): the reference's BackprojectDepth and Project3D
@@ -183,16 +195,10 @@ def rigid_flow(depth, T, K, inv_K=None, flow=None, valid=None, alpha=0.01, beta=
     alpha, beta, eps = not_negative(who, alpha=alpha, beta=beta, eps=eps)
     if excess and flow is None:
         raise DvsError("%s: excess=True needs a flow" % who)
-    d, d_image, d_row = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
-    mat = lambda m: m.detach().expand(N, 4, 4).contiguous()
-    T, K = mat(T), mat(K)
-    inv_K = mat(inv_K) if inv_K is not None else torch.linalg.inv(K).contiguous()
-    f, f_image, f_plane, f_row = _rows(flow.detach()) if flow is not None else (None, 0, 0, 0)
-    valid = valid.contiguous() if valid is not None else None
+    (d, d_image, d_row), K, inv_K, T, (f, f_image, f_plane, f_row), valid, p = _geometry(N, depth, K, inv_K, flow, valid, T, True)
     rigid = torch.empty((N, 2, H, W), device=d.device, dtype=torch.float32)
     label = torch.empty((N, H, W), device=d.device, dtype=torch.uint8) if f is not None else None
     over = torch.empty((N, H, W), device=d.device, dtype=torch.float32) if excess else None
-    p = lambda t: t.data_ptr() if t is not None else None
     check(_lib.lib().dvs_rigid_flow(d.data_ptr(), d_image, d_row, K.data_ptr(), inv_K.data_ptr(), T.data_ptr(), p(f), f_image, f_plane,
                                     f_row, p(valid), rigid.data_ptr(), p(over), p(label), N, H, W, alpha, beta, eps, _lib.stream()),
           "dvs_rigid_flow")
@@ -235,13 +241,7 @@ def fit_pose(depth, flow, K, inv_K=None, T0=None, valid=None, iters=4, huber=1.0
     if not huber > 0.0:
         raise DvsError("%s: huber=%r must be above 0 (inf: plain least squares)" % (who, huber))
     damping, eps = not_negative(who, damping=damping, eps=eps)
-    d, d_image, d_row = _planes(depth.detach() if depth.dim() == 3 else depth.detach()[:, 0])
-    mat = lambda m: m.detach().expand(N, 4, 4).contiguous()
-    K = mat(K)
-    inv_K = mat(inv_K) if inv_K is not None else torch.linalg.inv(K).contiguous()
-    T0 = mat(T0) if T0 is not None else torch.eye(4, device=d.device, dtype=torch.float32).repeat(N, 1, 1)
-    f, f_image, f_plane, f_row = _rows(flow.detach())
-    valid = valid.contiguous() if valid is not None else None
+    (d, d_image, d_row), K, inv_K, T0, (f, f_image, f_plane, f_row), valid, p = _geometry(N, depth, K, inv_K, flow, valid, T0, False)
     lib = _lib.lib()
     need = int(lib.dvs_pose_fit_workspace(N, H, W))
     if workspace is None:
@@ -251,7 +251,6 @@ def fit_pose(depth, flow, K, inv_K=None, T0=None, valid=None, iters=4, huber=1.0
     T = torch.empty((N, 4, 4), device=d.device, dtype=torch.float32)
     status = torch.empty((N,), device=d.device, dtype=torch.int32)
     sums = torch.empty((N, POSE_SUMS), device=d.device, dtype=torch.float64) if normal else None
-    p = lambda t: t.data_ptr() if t is not None else None
     check(lib.dvs_pose_fit(d.data_ptr(), d_image, d_row, K.data_ptr(), inv_K.data_ptr(), T0.data_ptr(), f.data_ptr(), f_image, f_plane,
                            f_row, p(valid), T.data_ptr(), status.data_ptr(), p(sums), workspace.data_ptr(),
                            workspace.numel() * workspace.element_size(), N, H, W, iters, huber, damping, eps, _lib.stream()),
